@@ -16,6 +16,11 @@ HBM when the timed region starts, results delivered to page-locked HOST buffers 
 Frames / faces shard across ranks with no data-path collective (weak scaling: per-rank work is
 fixed); the only collective is the one-time RCCL broadcast of the packed weights from rank 0, issued
 by the engine itself (pf_broadcast_weights -> ncclBroadcast).  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps and reports them (value, ms_per_step).  --full adds everything else the
+benchmark measures or checks (graph replay vs eager launch, sustained loop, per-kernel table and roofline, latency / PCIe /
+JPEG probes, the other BASELINE configurations, the CPU baseline).  --dump-outputs DIR writes what the last timed step
+delivered as DIR/<name>.npy (float32); the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -166,7 +171,47 @@ def parse_args():
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="plumbing check without a GPU: launch / rendezvous (gloo) / weight-blob broadcast / frame sharding "
                          "only, no compute, value = null (used by the CPU test tier; never a measurement)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the benchmark measures or checks: graph replay vs eager "
+                         "launch, the sustained loop, the per-kernel table and roofline, the one-lane / latency / PCIe / JPEG "
+                         "probes, the other configurations and the CPU baseline.  Off: set up, warm up, time the steps, "
+                         "write --dump-outputs, print the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path delivered in its last timed step (rank 0) as DIR/<name>.npy, float32")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    if args.dump_profile and not args.full:
+        ap.error("--dump-profile writes the per-kernel table, which only --full measures")
+    return args
+
+
+DUMP_BUDGET_BYTES = 60_000_000         # --dump-outputs stays under 64 MB, headers included
+
+
+def timed_outputs(state) -> dict:
+    """What a caller of the timed path receives from one step, as float32 host arrays: the pipeline's per-frame face counts and
+    per-face boxes / landmarks / scores (the page-locked buffers the step copies into), or the landmark workload's landmarks and
+    scores (device resident)."""
+    if hasattr(state, "h_kps"):
+        arrays = {"counts": state.h_counts, "boxes": state.h_boxes, "landmarks": state.h_kps, "scores": state.h_scores}
+    else:
+        arrays = {"landmarks": state.loc.cpu().numpy().reshape(-1, 98, 2), "scores": state.score.cpu().numpy()}
+    return {k: np.array(v, dtype=np.float32) for k, v in arrays.items()}
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """DIR/<name>.npy for every array; above DUMP_BUDGET_BYTES in all, each array keeps a fixed, seeded subset of its rows
+    (sorted, the same in every run) so two runs stay comparable row for row."""
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, int(a.shape[0] * DUMP_BUDGET_BYTES // total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -559,12 +604,15 @@ def main():
         per_rank_rate = [round(faces_per_step * args.steps / float(e.item()), 1) for e in every]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, timed_outputs(state))
     barrier()
-    state.check()
+    if args.full:
+        state.check()
 
     # ---- sustained loop (not the headline): long enough for an external GPU-busy sampler to see -------------------
     sustained = None
-    if not args.no_probes and args.sustain_s > 0:
+    if args.full and not args.no_probes and args.sustain_s > 0:
         n_sus = 0
         t1 = time.perf_counter()
         while time.perf_counter() - t1 < args.sustain_s:
@@ -577,7 +625,7 @@ def main():
 
     # ---- per-kernel device time (HIP events on the engine's own stream), dominant kernel roofline ---
     PROF_STEPS = 3
-    prof = {} if args.no_kernel_table else state.profile(PROF_STEPS)
+    prof = state.profile(PROF_STEPS) if args.full and not args.no_kernel_table else {}
     faces_per_launch = faces_per_step // lanes      # the profiled lane processes 1/lanes of the step
     frames_per_launch = args.frames // lanes
     # front mode (pf_batch's front engine): letterbox + detector + NMS run ONCE per step on all frames; their tags live in a profile of
@@ -637,10 +685,10 @@ def main():
                        "kernels": {k: {"ms_per_step": v[0] / PROF_STEPS, "launches_per_step": v[1] / PROF_STEPS}
                                    for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])}}, f, indent=1)
     one_lane = None
-    if workload == "pipeline" and hasattr(state, "one_lane_rate") and not args.no_probes:
+    if args.full and workload == "pipeline" and hasattr(state, "one_lane_rate") and not args.no_probes:
         one_lane = round(state.one_lane_rate(max(4, min(args.steps, 12))), 1)
     latency = None
-    if workload == "pipeline" and not args.no_probes:
+    if args.full and workload == "pipeline" and not args.no_probes:
         l1 = state.latency_p50(1)
         lN = state.latency_p50(args.frames // lanes)
         latency = {"single_frame_call_ms_p50": round(l1[0], 4), "single_frame_call_ms_p99": round(l1[1], 4),
@@ -649,7 +697,7 @@ def main():
                    "note": "synchronous pf_run_frames call on one stream, device-resident frames"}
     # ---- PCIe-inclusive rate (never the headline): same step with the frames in page-locked HOST memory ----------
     pcie = None
-    if workload == "pipeline" and rank == 0 and world == 1 and hasattr(state, "enable_host_frames") and not args.no_probes:
+    if args.full and workload == "pipeline" and rank == 0 and world == 1 and hasattr(state, "enable_host_frames") and not args.no_probes:
         state.enable_host_frames()
         hs = max(2, min(args.steps, 8))
         state.step_host()
@@ -666,7 +714,7 @@ def main():
                         "stream; results stay on the device (9.5 KB/frame)"}
     # ---- JPEG-file ingest (never the headline): the same step starting from baseline JPEG files in host memory --------
     jpeg = None
-    if workload == "pipeline" and rank == 0 and world == 1 and hasattr(state, "enable_jpeg_frames") and not args.no_probes:
+    if args.full and workload == "pipeline" and rank == 0 and world == 1 and hasattr(state, "enable_jpeg_frames") and not args.no_probes:
         try:
             import PIL  # noqa: F401  (only to WRITE the test files; the decoder is the engine's)
             have_pil = True
@@ -700,7 +748,7 @@ def main():
             jpeg = {"skipped": "%s: %s" % (type(e).__name__, e)}
     # ---- the other single-GPU configurations of BASELINE.json, a few steps each (never the headline) -----------------------------
     other = None
-    if workload == "pipeline" and args.model == "student" and rank == 0 and world == 1 and not args.no_probes:
+    if args.full and workload == "pipeline" and args.model == "student" and rank == 0 and world == 1 and not args.no_probes:
         other = {}
         try:      # configs[1]: 256 pre-cropped faces through Student@256 on ONE engine / stream (lane 0's program)
             nb = min(256, faces_per_step // lanes)
@@ -808,43 +856,46 @@ def main():
                        bcast["via"], bcast["bytes"] / 1e6,
                        (" in %.3f ms = %.1f GB/s vs 153 GB/s per xGMI link" % (bcast["ms"], bcast["bytes"] / 1e9 / (bcast["ms"] * 1e-3)))
                        if (world > 1 and bcast["ms"] > 0) else (" (one rank: the broadcast is a local no-op, no rate to report)" if world == 1 else ""))},
-        # the timed region is short (20 steps ~ 0.3 s): the rate of the multi-second loop that follows it, same steps, same process
-        "sustained_value": (round(sustained["faces_per_s_per_gpu"] * world, 1) if sustained else None),
-        # NOT the headline: the same configuration with decoder.upsampler2.conv2 and the score head on ONE f16 product (extra.other_configs
-        # has the note and the parity test's name); the headline stays f32-grade everywhere
-        "value_with_one_product_decoder_tail": ((other or {}).get("configs[2] with up2.conv2 + the score head on ONE f16 product (--mix hero,head)", {}).get("faces_per_s")),
-        "roofline": roofline,
-        "cpu_baseline": None,
         "extra": {"ms_per_frame": round(ms_per_step / args.frames, 4) if workload == "pipeline" else None,
                   "algorithmic_tflops": round(value * GFLOP_PER_FACE[args.model] / 1e3, 2),
                   "frac_of_conv_roofline": round(value / world * GFLOP_PER_FACE[args.model] / 1e3 / PEAK_TFLOPS[args.dtype], 4),
-                  "hbm_ops": (dict(hbm_ops_table(prof, PROF_STEPS, frames_per_launch, faces_per_launch, tuple(args.frame_hw), args.faces_per_frame),
-                                   **hbm_ops_table(front_prof, PROF_STEPS, args.frames, faces_per_step, tuple(args.frame_hw), args.faces_per_frame))
-                              if workload == "pipeline" else None),
-                  "dense_kernels": dense_kernel_table(prof, PROF_STEPS, faces_per_launch, args.dtype, committed_pmc_traffic(faces_per_launch)) if args.model == "student" else None,
-                  "sustained": sustained,
-                  "executed_mfma_frac_forward": exec_frac_forward,
-                  # what ONE engine / one stream delivers on a lane's share of the step (plain pf_run_frames, graph replay);
-                  # the headline is pf_batch_run_frames over `lanes` of them
-                  "one_lane_faces_per_s": one_lane,
-                  "latency": latency,
-                  "pcie_inclusive": pcie, "jpeg_ingest": jpeg, "other_configs": other,
                   "weight_broadcast": bcast,
                   "per_rank_faces_per_s": per_rank_rate,      # each rank on its own clock; `value` uses the slowest rank's time
                   "weight_broadcast_GBps_vs_xgmi_link": (round(bcast["bytes"] / 1e9 / (bcast["ms"] * 1e-3), 2) if (world > 1 and bcast["ms"] > 0) else None),
-                  "setup_s": round(setup_s, 2),
-                  "kernel_ms_per_lane_step": {k: round(v[0] / PROF_STEPS, 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])[:12]},
-                  "lane_step_ms_serial": round(serial_ms, 4),
-                  # front engine: letterbox + detector + NMS of ALL frames of a step, once (null: every lane detects its own slice)
-                  "front_step_ms_serial": round(front_ms, 4) if front_prof else None,
-                  "front_kernel_ms_per_step": ({k: round(v[0] / PROF_STEPS, 4) for k, v in sorted(front_prof.items(), key=lambda kv: -kv[1][0])[:8]}
-                                               if front_prof else None),
-                  "step_ms_serial": round(step_serial_ms, 4),
-                  # how much of a step's serial kernel time the concurrent streams hide: (front + lanes x lane) / measured step
-                  "lanes_overlap": round(step_serial_ms / ms_per_step, 4)},
+                  "setup_s": round(setup_s, 2)},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(args.cpu_faces, tuple(args.frame_hw), args.faces_per_frame)
+    if args.full:
+        out.update({
+            # the timed region is short (20 steps ~ 0.3 s): the rate of the multi-second loop that follows it, same steps, same process
+            "sustained_value": (round(sustained["faces_per_s_per_gpu"] * world, 1) if sustained else None),
+            # NOT the headline: the same configuration with decoder.upsampler2.conv2 and the score head on ONE f16 product (extra.other_configs
+            # has the note and the parity test's name); the headline stays f32-grade everywhere
+            "value_with_one_product_decoder_tail": ((other or {}).get("configs[2] with up2.conv2 + the score head on ONE f16 product (--mix hero,head)", {}).get("faces_per_s")),
+            "roofline": roofline,
+            "cpu_baseline": None})
+        out["extra"].update({
+            "hbm_ops": (dict(hbm_ops_table(prof, PROF_STEPS, frames_per_launch, faces_per_launch, tuple(args.frame_hw), args.faces_per_frame),
+                             **hbm_ops_table(front_prof, PROF_STEPS, args.frames, faces_per_step, tuple(args.frame_hw), args.faces_per_frame))
+                        if workload == "pipeline" else None),
+            "dense_kernels": dense_kernel_table(prof, PROF_STEPS, faces_per_launch, args.dtype, committed_pmc_traffic(faces_per_launch)) if args.model == "student" else None,
+            "sustained": sustained,
+            "executed_mfma_frac_forward": exec_frac_forward,
+            # what ONE engine / one stream delivers on a lane's share of the step (plain pf_run_frames, graph replay);
+            # the headline is pf_batch_run_frames over `lanes` of them
+            "one_lane_faces_per_s": one_lane,
+            "latency": latency,
+            "pcie_inclusive": pcie, "jpeg_ingest": jpeg, "other_configs": other,
+            "kernel_ms_per_lane_step": {k: round(v[0] / PROF_STEPS, 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])[:12]},
+            "lane_step_ms_serial": round(serial_ms, 4),
+            # front engine: letterbox + detector + NMS of ALL frames of a step, once (null: every lane detects its own slice)
+            "front_step_ms_serial": round(front_ms, 4) if front_prof else None,
+            "front_kernel_ms_per_step": ({k: round(v[0] / PROF_STEPS, 4) for k, v in sorted(front_prof.items(), key=lambda kv: -kv[1][0])[:8]}
+                                         if front_prof else None),
+            "step_ms_serial": round(step_serial_ms, 4),
+            # how much of a step's serial kernel time the concurrent streams hide: (front + lanes x lane) / measured step
+            "lanes_overlap": round(step_serial_ms / ms_per_step, 4)})
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(args.cpu_faces, tuple(args.frame_hw), args.faces_per_frame)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

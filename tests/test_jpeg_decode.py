@@ -199,10 +199,10 @@ def test_decode_matches_libjpeg_emulator(emu_library):
         eng.close()
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/figure/test1.jpg"), reason="reference checkout not present (GPU box)")
 def test_reference_sample_image_emulator(emu_library):
-    """The reference's own sample (figure/test1.jpg), as demo.py would cv2.imread it."""
-    data = open("/root/reference/figure/test1.jpg", "rb").read()
+    """The reference's own sample (figure/test1.jpg, stored as tests/golden/reference_test1.jpg), as demo.py would cv2.imread it."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_test1.jpg"), "rb") as f:
+        data = f.read()
     eng = _native.Engine(0, emu_library)
     try:
         _, h, w, got = eng.decode_jpeg(data)

@@ -17,7 +17,7 @@ for vi, spec in enumerate(sys.argv[2:]):
             k, v = kv.split("=", 1)
             env[k] = v
     out = "gpurun_out/ab_%d.json" % vi
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--no-probes",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--no-probes",
                         "--dump-profile", out] + extra, env=env, capture_output=True, text=True)
     try:
         d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -4,7 +4,7 @@ tagsub = sys.argv[1] if len(sys.argv) > 1 else "mbconv"
 for lib in sorted(glob.glob("variants/lib_*.so")):
     env = dict(os.environ, PEPPA_HIP_LIBRARY=os.path.abspath(lib))
     out = f"gpurun_out/prof_{os.path.basename(lib)}.json"
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--dump-profile", out],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--dump-profile", out],
                        env=env, capture_output=True, text=True)
     try:
         d = json.loads(r.stdout.strip().splitlines()[-1])

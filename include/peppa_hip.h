@@ -185,7 +185,7 @@ int pf_decode_jpeg_batch(pf_handle* h, int n, const uint8_t* const* jpegs, const
  * One-Euro filter core/smoother/lk.py:19-56,117-149, hull boxes facer.py:70-81).  Here all of it is device kernels over
  * device state (float64, as the reference computes it under its pinned numpy): per frame the host reads back 8 bytes (the
  * frame-difference sum that gates the detector, facer.py:98-118) and the results.  One handle = one stream; shard streams,
- * never one stream, across handles / GPUs.  Outputs: *n_out faces (<= top_k); boxes [n][4] = the new track boxes, kps
+ * never one stream, across handles / GPUs (several streams on one handle: pf_track_streams below).  Outputs: *n_out faces (<= top_k); boxes [n][4] = the new track boxes, kps
  * [n][98][2] = the smoothed landmarks (both float64), scores [n][98]; *detector_ran says whether the gate ran the detector.
  * track_iou_thres / smooth_box = Skps.yml Trace.iou_thres / Trace.smooth_box, diff_thres = 5 in the reference. */
 int pf_track_frame(pf_handle* h, const uint8_t* bgr, int mem, int height, int width, int row_stride,
@@ -199,6 +199,29 @@ int pf_track_frame_planted(pf_handle* h, const uint8_t* bgr, int mem, int height
                            const float* det_rows, int rows, float score_thres, float nms_iou_thres, float min_face, int top_k,
                            float track_iou_thres, float smooth_box, float diff_thres,
                            int* n_out, double* boxes, double* kps, float* scores, int* detector_ran);
+
+/* N independent video streams on one handle (one camera feed = one stream): state of stream s lives in slot s
+ * (0 <= s < max_streams), each slot holding the tracking state of pf_track_frame plus the stream's previous frame.
+ * (Re)allocates the pool and forgets every stream.  Independent of pf_track_frame's own stream on the same handle. */
+int pf_track_streams_config(pf_handle* h, int max_streams, int top_k);
+/* One FaceAna.run() per listed stream: frames [n][height][width][3] packed BGR (mem = PF_MEM_HOST or PF_MEM_DEVICE),
+ * frame i belongs to stream stream_ids[i] (distinct within a call; a stream absent from a call keeps its state and its
+ * previous frame).  Per stream the semantics are those of pf_track_frame on its own handle, including a frame whose size
+ * differs from the stream's previous frame counting as "no previous frame"; all frames of one call share one size.
+ * det_rows: NULL = the detector's own rows, else planted decoded rows [n][rows][16], used only for the frames whose gate
+ * runs the detector (test / benchmark instrument, as in pf_run_frames_planted).  The gate of all n frames is one kernel
+ * and one read-back; the detector runs once on the frames whose gate opened, the landmark stage once on n x top_k slots.
+ * Needs n <= max_streams, n <= the detector program's max_batch and n * top_k <= the landmark program's max_batch.
+ * Outputs (host): counts[n], boxes [n][top_k][4] f64, kps [n][top_k][98][2] f64, scores [n][top_k][98] f32 (rows
+ * beyond counts[i] are undefined), detector_ran[n]; boxes / kps / scores / detector_ran may be NULL.  A rejected call
+ * (bad ids, sizes, no pool) changes no stream.  If the range guard fails the call, every stream of the call is reset
+ * (the others keep their state) and the error names the program slot.  Never captured into a hipGraph. */
+int pf_track_streams(pf_handle* h, int n, const int* stream_ids, const uint8_t* frames, int mem, int height, int width,
+                     const float* det_rows, int rows, float score_thres, float nms_iou_thres, float min_face,
+                     float track_iou_thres, float smooth_box, float diff_thres,
+                     int* counts, double* boxes, double* kps, float* scores, int* detector_ran);
+/* FaceAna.reset() of one stream (stream_id >= 0) or of all (-1). */
+int pf_track_streams_reset(pf_handle* h, int stream_id);
 
 /* Frame ingest (replaces the pageable numpy arrays cv2.imread / VideoCapture.read hand to
  * FaceAna.run, demo.py:13-17,76): page-locked host memory for frame batches (decode straight into it) and for

@@ -59,6 +59,12 @@ def _declare(lib):
     lib.pf_track_frame_planted.restype = i
     lib.pf_track_reset.argtypes = [vp]
     lib.pf_track_reset.restype = i
+    lib.pf_track_streams_config.argtypes = [vp, i, i]
+    lib.pf_track_streams_config.restype = i
+    lib.pf_track_streams.argtypes = [vp, i, ip, vp, i, i, i, fp, i, f, f, f, f, f, f, ip, dp, dp, fp, ip]
+    lib.pf_track_streams.restype = i
+    lib.pf_track_streams_reset.argtypes = [vp, i]
+    lib.pf_track_streams_reset.restype = i
     lib.pf_run_frames.argtypes = [vp, vp, i, i, i, i, f, f, f, i, vp, vp, vp, vp, i]
     lib.pf_run_frames_planted.argtypes = [vp, vp, i, i, i, i, vp, i, f, f, f, i, vp, vp, vp, vp, i]
     lib.pf_letterbox.argtypes = [vp, vp, i, i, i, i, i, i, vp, fp]
@@ -561,6 +567,55 @@ class Engine:
     def track_reset(self):
         self._check(self.lib.pf_track_reset(self.h), "pf_track_reset")
         self._resident_shape = None
+
+    # ---- N video streams on this engine (pf_track_streams) ----------------------------------------------------------------
+    def track_streams_config(self, max_streams: int, top_k: int):
+        """(Re)allocate the pool of stream slots 0 .. max_streams-1 (every stream forgotten)."""
+        self._check(self.lib.pf_track_streams_config(self.h, int(max_streams), int(top_k)), "pf_track_streams_config")
+        self._streams_top_k = int(top_k)
+
+    def track_streams(self, stream_ids, frames, score_thres: float, nms_iou_thres: float, min_face: float,
+                      track_iou_thres: float = 0.5, smooth_box: float = 0.3, diff_thres: float = 5.0,
+                      planted_rows: Optional[np.ndarray] = None, shape=None):
+        """FaceAna.run() of each listed stream on its frame.  frames: numpy uint8 [n,H,W,3], or a device pointer (int) with
+        shape=(n, H, W).  planted_rows (test instrument): decoded detector rows [n,R,16], used for the frames whose gate runs
+        the detector.  Returns one (boxes float64 [c,4], kps float64 [c,98,2], scores float32 [c,98], detector_ran) per frame."""
+        ids = np.ascontiguousarray(stream_ids, np.int32).reshape(-1)
+        if isinstance(frames, int):
+            if shape is None:
+                raise ValueError("a device pointer needs shape=(n, H, W)")
+            n, H, W = (int(x) for x in shape)
+            fptr, fmem, keep = C.c_void_p(frames), PF_MEM_DEVICE, None
+        else:
+            keep = np.ascontiguousarray(frames)
+            if keep.dtype != np.uint8 or keep.ndim != 4 or keep.shape[3] != 3:
+                raise ValueError("frames must be uint8 [n,H,W,3]")
+            n, H, W = keep.shape[:3]
+            fptr, fmem = _ptr(keep), PF_MEM_HOST
+        if ids.shape[0] != n:
+            raise ValueError("one stream id per frame")
+        K = max(1, getattr(self, "_streams_top_k", 1))    # before config the engine rejects the call itself
+        counts = np.zeros((n,), np.int32)
+        ran = np.zeros((n,), np.int32)
+        boxes = np.zeros((n, K, 4), np.float64)
+        kps = np.zeros((n, K, 98, 2), np.float64)
+        scores = np.zeros((n, K, 98), np.float32)
+        pr, R = None, 0
+        if planted_rows is not None:
+            pr = np.ascontiguousarray(planted_rows, np.float32)
+            R = pr.shape[1]
+        rc = self.lib.pf_track_streams(self.h, n, ids.ctypes.data_as(C.POINTER(C.c_int)), fptr, fmem, H, W,
+                                       pr.ctypes.data_as(C.POINTER(C.c_float)) if pr is not None else None, R,
+                                       float(score_thres), float(nms_iou_thres), float(min_face), float(track_iou_thres),
+                                       float(smooth_box), float(diff_thres), counts.ctypes.data_as(C.POINTER(C.c_int)),
+                                       boxes.ctypes.data_as(C.POINTER(C.c_double)), kps.ctypes.data_as(C.POINTER(C.c_double)),
+                                       scores.ctypes.data_as(C.POINTER(C.c_float)), ran.ctypes.data_as(C.POINTER(C.c_int)))
+        self._check(rc, "pf_track_streams")
+        return [(boxes[i, :c].copy(), kps[i, :c].copy(), scores[i, :c].copy(), bool(ran[i]))
+                for i, c in enumerate(counts.tolist())]
+
+    def track_streams_reset(self, stream_id: int = -1):
+        self._check(self.lib.pf_track_streams_reset(self.h, int(stream_id)), "pf_track_streams_reset")
 
     def set_option(self, option: int, value: int):
         """PF_OPT_HIP_GRAPH (1): replay device-resident run_frames calls from a captured hipGraph."""

@@ -1,0 +1,81 @@
+"""StreamTracker: ``FaceAna.run()`` with tracking for N camera feeds on one engine.
+
+``StreamTracker(max_streams=N).run({stream_id: frame, ...}) -> {stream_id: [{'box', 'kps', 'scores'}, ...]}`` advances
+every listed stream by one frame in one engine call (``pf_track_streams``): the frame-difference gate of all of them is
+one kernel and one read-back, the detector runs once on the frames whose gate opened, the landmark stage once on all of
+them, and the frame-to-frame state (track boxes, landmark sets, One-Euro filters, previous frame) of stream s stays on
+the device in slot s.  Per stream the answers are those of a ``FaceAna`` with ``device_tracking`` on its own engine.
+A stream absent from a call keeps its state; ``reset(stream_id)`` is ``FaceAna.reset()`` of one stream."""
+from __future__ import annotations
+
+import logging
+import pathlib
+from typing import Dict, Optional
+
+import numpy as np
+
+from ... import _native
+from ...logger.logger import logger
+from .facer import _load_weights, get_cfg
+from .hip_model_base import HIPEngine, run_guarded
+
+
+class StreamTracker:
+    def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, max_streams: int = 8,
+                 device: Optional[int] = None, library: Optional[str] = None, verbose: bool = False):
+        if verbose:
+            logger.setLevel(logging.DEBUG)
+        if int(max_streams) < 1:
+            raise ValueError("max_streams must be >= 1")
+        cfg = cfg or get_cfg()
+        sk = cfg["Skps"]
+        eng_cfg = sk.get("Engine", {})
+        dev = int(eng_cfg.get("device", 0)) if device is None else int(device)
+        dtype = eng_cfg.get("dtype", "f32")
+        root = pathlib.Path(__file__).resolve().parents[2]
+        weights = weights or {}
+        det_w = weights.get("detector") or _load_weights(root, sk["Detect"]["model_path"], "detector")
+        kps_arch = str(sk["Keypoints"].get("model", "student"))
+        kps_w = weights.get("keypoints") or _load_weights(root, sk["Keypoints"]["model_path"], "teacher" if kps_arch == "teacher" else "keypoints")
+
+        self.max_streams = int(max_streams)
+        self.top_k = int(sk["Detect"]["topk"])
+        self._det_cfg = sk["Detect"]
+        self.min_face = sk["Detect"]["min_face"]
+        self.iou_thres = sk["Trace"]["iou_thres"]
+        self.alpha = sk["Trace"]["smooth_box"]
+        self.diff_thres = 5
+        self._planted_rows = None    # test instrument: callable(stream_ids, frames [n,H,W,3]) -> decoded detector rows [n,R,16]
+        self.engine = _native.Engine(dev, library)
+        # both programs sized for a call that advances every stream: one detector frame and top_k faces per stream
+        self.detector = HIPEngine(det_w, "detector", sk["Detect"]["input_shape"], dtype=dtype, max_batch=self.max_streams,
+                                  engine=self.engine)
+        self.landmark = HIPEngine(kps_w, "keypoints", sk["Keypoints"]["input_shape"], dtype=dtype,
+                                  max_batch=self.max_streams * self.top_k, engine=self.engine, arch=kps_arch)
+        self.engine.track_streams_config(self.max_streams, self.top_k)
+        self.last_detector_ran: Dict[int, bool] = {}
+        logger.info("stream tracker init done (%d streams)", self.max_streams)
+
+    def run(self, frames: Dict[int, np.ndarray]) -> Dict[int, list]:
+        """One FaceAna.run() per listed stream; all frames of a call have one size."""
+        if not frames:
+            return {}
+        ids = [int(s) for s in frames]
+        batch = np.stack([np.ascontiguousarray(frames[s]) for s in frames])
+        planted = self._planted_rows(ids, batch) if self._planted_rows is not None else None
+        res = run_guarded([self.detector, self.landmark], self.engine.track_streams, ids, batch,
+                          float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]), float(self.min_face),
+                          float(self.iou_thres), float(self.alpha), float(self.diff_thres), planted)
+        self.last_detector_ran = {s: ran for s, (_, _, _, ran) in zip(ids, res)}   # did the gate run the detector
+        return {s: self.to_dict(b, k, sc) for s, (b, k, sc, _) in zip(ids, res)}
+
+    @staticmethod
+    def to_dict(bboxes, kps, states):
+        return [{"box": bboxes[i], "kps": kps[i], "scores": states[i]} for i in range(len(bboxes))]
+
+    def reset(self, stream_id: Optional[int] = None):
+        """FaceAna.reset() of one stream, or of every stream (None)."""
+        self.engine.track_streams_reset(-1 if stream_id is None else int(stream_id))
+
+    def close(self):
+        self.engine.close()

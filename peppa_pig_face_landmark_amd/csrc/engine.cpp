@@ -99,8 +99,9 @@ struct pf_handle {
     // selects the previous LDS-class-filter decoder front end instead of the register-blocked one
     unsigned long long* d_dbg = nullptr;   // PEPPA_DBG & 64: cycle accounting of sepup_pipe_kernel
     int dbg = 0;             // PEPPA_DBG: timing ablations of the GEMM kernels (ConvGemmArgs::dbg), never set in production
-    // tracking state of the handle's video stream (pf_track_frame, k_track.h)
-    TrackState track;
+    // tracking state of the handle's video stream (pf_track_frame: one slot) and of its pf_track_streams pool (k_track.h)
+    TrackPool track;
+    TrackPool streams;
     JpegState jpeg;          // pf_decode_jpeg (jpeg.inl)
     // f32s range guard (pf_common.h pf_amax, k_layers.h range_verdict_kernel): on for every forward unless switched off with
     // PF_OPT_RANGE_CHECK = 0; the slots live with each program
@@ -1290,6 +1291,7 @@ void pf_destroy(pf_handle* h) {
     if (h->h_status) (void)hipHostFree(h->h_status);
     h->pipe.release();
     h->track.release();
+    h->streams.release();
     h->jpeg.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);

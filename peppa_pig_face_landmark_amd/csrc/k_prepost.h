@@ -93,6 +93,8 @@ struct LetterboxArgs {
     double scale_x, scale_y;      // 1/(rw/W), 1/(rh/H) as OpenCV derives them
     int pad_value;
     int keep_order;               // 1: no BGR -> RGB swap (plain cv2.resize, pf_resize)
+    const int* frame_idx;         // optional [F]: output f reads frames[frame_idx[f]] (the detector frames of a
+                                  // pf_track_streams call); nullptr = identity
 };
 
 __global__ __launch_bounds__(256) void letterbox_kernel(LetterboxArgs a) {
@@ -106,7 +108,8 @@ __global__ __launch_bounds__(256) void letterbox_kernel(LetterboxArgs a) {
         o[0] = o[1] = o[2] = (unsigned char)a.pad_value;
         return;
     }
-    const unsigned char* src = a.frames + (size_t)f * a.H * a.row_stride;
+    const int fs = a.frame_idx ? a.frame_idx[f] : f;
+    const unsigned char* src = a.frames + (size_t)fs * a.H * a.row_stride;
     int r[3];
     if (a.W == 2 * a.rw && a.H == 2 * a.rh) {
         const unsigned char* p0 = src + (size_t)(2 * ry) * a.row_stride + (size_t)(2 * rx) * 3;
@@ -332,6 +335,7 @@ struct CropParamArgs {
     float min_face;       // 20 (face_landmark.py:26)
     double width_factor;  // 1 + 2*extend[0]  (face_landmark.py:83)
     const int* boxes64_f32;   // device flag: the rows of boxes64 hold float32 values and numpy would compute in float32 (k_track.h)
+    const int* boxes64_f32_frame;   // opt-in [n / per_frame]: the same flag per frame (pf_track_streams); overrides boxes64_f32
 };
 
 __global__ __launch_bounds__(64) void crop_params_kernel(CropParamArgs a) {
@@ -343,7 +347,8 @@ __global__ __launch_bounds__(64) void crop_params_kernel(CropParamArgs a) {
     for (int k = 0; k < 5; ++k) cf[k] = 0.f;
     if (a.counts && (i % a.per_frame) >= a.counts[i / a.per_frame]) return;
     float bf[4];
-    const bool as_f32 = a.boxes64 && a.boxes64_f32 && *a.boxes64_f32 != 0;
+    const bool as_f32 = a.boxes64 && (a.boxes64_f32_frame ? a.boxes64_f32_frame[i / a.per_frame] != 0
+                                                          : (a.boxes64_f32 && *a.boxes64_f32 != 0));
     if (as_f32) for (int k = 0; k < 4; ++k) bf[k] = (float)a.boxes64[(size_t)i * 4 + k];
     if (a.boxes64 && !as_f32) {
         const double* b = a.boxes64 + (size_t)i * 4;

@@ -1,33 +1,137 @@
-// pf_track_frame / pf_track_reset: FaceAna.run() / reset() for one video stream with the tracking state on the device
-// (included at the end of engine.cpp; kernels in k_track.h).
+// pf_track_frame / pf_track_reset: FaceAna.run() / reset() for one video stream with the tracking state on the device;
+// pf_track_streams*: the same for N streams on one handle, one call advancing any subset of them by one frame each
+// (included at the end of engine.cpp; kernels in k_track.h).  Both run the same stream-batched kernels (track_enqueue).
 namespace {
 
-const int kTrackMaxNow = 1024;   // rows NMS can keep per frame
-
-int ensure_track(pf_handle* h, int top_k) {
-    TrackState& t = h->track;
-    if (t.top_k >= top_k && t.d_track_box) return 0;
+// (Re)allocate a pool of S slots for up to K faces each; every slot forgets its stream.
+int track_pool_alloc(pf_handle* h, TrackPool& P, int S, int K) {
     PF_HIP(h, hipStreamSynchronize(h->stream));
-    t.release();
-    const size_t lm = (size_t)top_k * 196 * sizeof(double);
-    PF_HIP(h, hipMalloc((void**)&t.d_track_box, (size_t)kTrackMaxNow * 4 * sizeof(double)));
-    PF_HIP(h, hipMalloc((void**)&t.d_judged, (size_t)kTrackMaxNow * 4 * sizeof(double)));
-    PF_HIP(h, hipMalloc((void**)&t.d_sel, (size_t)top_k * 4 * sizeof(double)));
-    PF_HIP(h, hipMalloc((void**)&t.d_hull, (size_t)top_k * 4 * sizeof(double)));
-    PF_HIP(h, hipMalloc((void**)&t.d_scores, (size_t)top_k * 98 * sizeof(float)));
-    for (int k = 0; k < 2; ++k) {
-        PF_HIP(h, hipMalloc((void**)&t.d_lm[k], lm));
-        PF_HIP(h, hipMalloc((void**)&t.d_dx[k], lm));
-        PF_HIP(h, hipMalloc((void**)&t.d_n_lm[k], sizeof(int)));
+    P.release();
+    TrackPoolView& v = P.v;
+    const size_t s = (size_t)S, k = (size_t)K;
+    PF_HIP(h, hipMalloc((void**)&v.track_box, s * kTrackMaxNow * 4 * sizeof(double)));
+    PF_HIP(h, hipMalloc((void**)&v.judged, s * kTrackMaxNow * 4 * sizeof(double)));
+    PF_HIP(h, hipMalloc((void**)&v.lm, s * 2 * k * 196 * sizeof(double)));
+    PF_HIP(h, hipMalloc((void**)&v.dx, s * 2 * k * 196 * sizeof(double)));
+    PF_HIP(h, hipMalloc((void**)&v.sel, s * k * 4 * sizeof(double)));
+    PF_HIP(h, hipMalloc((void**)&v.hull, s * k * 4 * sizeof(double)));
+    PF_HIP(h, hipMalloc((void**)&v.out_box, s * k * 4 * sizeof(double)));
+    PF_HIP(h, hipMalloc((void**)&v.out_lm, s * k * 196 * sizeof(double)));
+    PF_HIP(h, hipMalloc((void**)&v.scores, s * k * 98 * sizeof(float)));
+    PF_HIP(h, hipMalloc((void**)&v.n_track, s * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.n_lm, s * 2 * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.f32, s * 4 * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.n_judged, s * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.n_sel, s * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.sel_f32, s * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.out_count, s * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&P.d_desc, s * sizeof(TrackFrameDesc)));
+    PF_HIP(h, hipMemset(v.f32, 0, s * 4 * sizeof(int)));
+    PF_HIP(h, hipMemset(v.n_track, 0, s * sizeof(int)));
+    PF_HIP(h, hipMemset(v.n_lm, 0, s * 2 * sizeof(int)));
+    v.desc = P.d_desc;
+    v.K = v.top_k = K;
+    P.S = S;
+    P.K = K;
+    P.slots.assign(S, TrackSlot());
+    P.h_desc.assign(S, TrackFrameDesc{});
+    return 0;
+}
+
+// pf_track_frame's pool: one slot, reallocated (and the stream forgotten) only when a call asks for more faces
+int ensure_track(pf_handle* h, int top_k) {
+    if (h->track.K >= top_k && h->track.v.track_box) return 0;
+    return track_pool_alloc(h, h->track, 1, top_k);
+}
+
+// Steps 3-6 of FaceAna.run() for the n frames of a call whose gate has been evaluated (facer.py:55-81).  P.h_desc[0, n)
+// holds each frame's slot / ping-pong half / flags and its index among the n_det detector frames (or -1); h_det_idx[j] is
+// the call index of detector frame j and d_det_idx its device copy (nullptr when the detector frames are all n frames in
+// order).  planted: host rows [n][planted_rows][16] that replace the detector's own rows.  Everything is enqueued; the
+// results of frame i are in P.v.out_count / out_box / out_lm / scores [i] after the caller's synchronisation.
+int track_enqueue(pf_handle* h, TrackPool& P, int n, int top_k, const unsigned char* d_frames, int H, int W, int n_det,
+                  const int* h_det_idx, const int* d_det_idx, const float* planted, int planted_rows,
+                  float score_thres, float nms_iou_thres, float min_face, float track_iou_thres, float smooth_box) {
+    Program& det = h->prog[PF_NET_DETECTOR];
+    Program& lm = h->prog[PF_NET_LANDMARK];
+    const int rows = det.bufs[det.hdr.out_buf0].elems_per_item / 16;
+    if (planted && n_det > 0 && planted_rows != rows) PF_FAIL(h, "pf_track: %d planted rows, the detector produces %d", planted_rows, rows);
+    if (ensure_pipeline(h, std::max(n_det, 1), n * top_k, top_k, rows)) return 1;
+    TrackPoolView v = P.v;
+    v.top_k = top_k;
+    PF_HIP(h, hipMemcpyAsync(P.d_desc, P.h_desc.data(), (size_t)n * sizeof(TrackFrameDesc), hipMemcpyHostToDevice, h->stream));
+    // 1. detector + NMS on the frames whose gate opened, then judge_boxs against each stream's track boxes
+    if (n_det > 0) {
+        const LetterboxGeom g = letterbox_geom(H, W, det.hdr.in_h, det.hdr.in_w);
+        if (run_detector_stage(h, d_frames, n_det, H, W, W * 3, g, d_det_idx)) return 1;
+        const float* d_rows = (const float*)det.buf_ptr(det.hdr.out_buf0);
+        if (planted) {   // planted-candidate protocol: the network ran, its rows are replaced
+            const size_t fb = (size_t)rows * 16;
+            if (ensure_dev(h, h->pipe.d_rows_planted, h->pipe.rows_planted_bytes, (size_t)n_det * fb * sizeof(float))) return 1;
+            for (int j = 0; j < n_det;) {     // one copy per run of consecutive call indices
+                int e = j + 1;
+                while (e < n_det && h_det_idx[e] == h_det_idx[e - 1] + 1) ++e;
+                PF_HIP(h, hipMemcpyAsync(h->pipe.d_rows_planted + (size_t)j * fb, planted + (size_t)h_det_idx[j] * fb,
+                                         (size_t)(e - j) * fb * sizeof(float), hipMemcpyHostToDevice, h->stream));
+                j = e;
+            }
+            d_rows = h->pipe.d_rows_planted;
+        }
+        if (run_nms_stage(h, d_rows, rows, n_det, g, score_thres, nms_iou_thres, 0.f, 1, false)) return 1;
+        JudgeStageArgs ja{};
+        ja.v = v; ja.stage = TRACK_JUDGE_DETECTIONS;
+        ja.det_rows = h->pipe.d_keep_rows; ja.det_count = h->pipe.d_keep_count; ja.det_stride = kMaxKeep;
+        ja.iou_thres = track_iou_thres; ja.alpha = smooth_box;
+        PF_LAUNCH(track_judge_kernel, dim3(n), dim3(256), h->stream, ja);
     }
-    PF_HIP(h, hipMalloc((void**)&t.d_n_track, sizeof(int)));
-    PF_HIP(h, hipMalloc((void**)&t.d_n_judged, sizeof(int)));
-    PF_HIP(h, hipMalloc((void**)&t.d_n_sel, sizeof(int)));
-    PF_HIP(h, hipMalloc((void**)&t.d_f32, 4 * sizeof(int)));
-    PF_HIP(h, hipMemset(t.d_f32, 0, 4 * sizeof(int)));
-    t.top_k = top_k;
-    t.has_track = t.lm_valid = false;
-    t.cur = 0;
+    // 2. sort_and_filter -> boxes_return (float64 rows, stay on the device)
+    SelectArgs sa{};
+    sa.v = v; sa.min_face = min_face;
+    PF_LAUNCH(track_select_kernel, dim3(n), dim3(64), h->stream, sa);
+    // 3. landmark stage on the selected boxes: n x top_k slots, the per-frame counts read on the device
+    if (run_landmark_stage(h, d_frames, H, W, W * 3, h->pipe.d_sel_boxes, v.n_sel, n * top_k, top_k, v.sel, nullptr, v.sel_f32)) return 1;
+    // 4. One-Euro smoothing against the previous sets + hull boxes
+    PF_LAUNCH(track_count_kernel, dim3(n), dim3(64), h->stream, v, (const int*)h->pipe.d_crop_params);
+    GroupStageArgs ga{};
+    ga.v = v;
+    ga.kps = h->pipe.d_kps; ga.scores_in = (const float*)lm.buf_ptr(lm.hdr.out_buf1); ga.crop_params = h->pipe.d_crop_params;
+    ga.iou_thres = track_iou_thres; ga.scale_w = (double)W; ga.scale_h = (double)H;
+    ga.min_cutoff = 0.15; ga.beta = 0.8; ga.d_cutoff = 1.0;          // OneEuroFilter defaults, lk.py:100-101
+    PF_LAUNCH(track_group_kernel, dim3(top_k, n), dim3(128), h->stream, ga);
+    // 5. track_box = judge_boxs(boxes_return, hull boxes) (facer.py:70-81)
+    JudgeStageArgs jb{};
+    jb.v = v; jb.stage = TRACK_JUDGE_HULLS;
+    jb.iou_thres = track_iou_thres; jb.alpha = smooth_box;
+    PF_LAUNCH(track_judge_kernel, dim3(n), dim3(256), h->stream, jb);
+    // 6. results in call order
+    PF_LAUNCH(track_gather_kernel, dim3(n), dim3(256), h->stream, v);
+    for (int i = 0; i < n; ++i) {
+        TrackSlot& t = P.slots[P.h_desc[i].slot];
+        t.cur ^= 1;
+        t.lm_valid = true;
+        t.has_track = true;
+    }
+    return 0;
+}
+
+// previous-frame storage of a pf_track_streams pool, grown to frames of `bytes`; the frames it holds move with it
+int ensure_stream_frames(pf_handle* h, TrackPool& P, size_t bytes) {
+    if (bytes <= P.frame_slot_bytes && P.d_frames) return 0;
+    const size_t stride = (bytes + 255) / 256 * 256;
+    unsigned char* nf = nullptr;
+    PF_HIP(h, hipMalloc((void**)&nf, (size_t)P.S * stride));
+    if (P.d_frames) {
+        for (int s = 0; s < P.S; ++s) {
+            const TrackSlot& t = P.slots[s];
+            if (t.have_prev)
+                PF_HIP(h, hipMemcpyAsync(nf + (size_t)s * stride, P.d_frames + (size_t)s * P.frame_slot_bytes,
+                                         (size_t)t.prev_h * t.prev_w * 3, hipMemcpyDeviceToDevice, h->stream));
+        }
+        PF_HIP(h, hipStreamSynchronize(h->stream));
+        (void)hipFree(P.d_frames);
+    }
+    P.d_frames = nf;
+    P.frame_slot_bytes = stride;
     return 0;
 }
 
@@ -37,8 +141,7 @@ extern "C" {
 
 int pf_track_reset(pf_handle* h) {
     if (!h) return 1;
-    h->track.has_track = false;
-    h->track.lm_valid = false;
+    for (TrackSlot& t : h->track.slots) t.has_track = t.lm_valid = false;
     return pf_forget_frames(h);
 }
 
@@ -78,7 +181,8 @@ static int track_frame_impl(pf_handle* h, const uint8_t* bgr, int mem, int heigh
     if (!bgr || !n_out || top_k < 1 || top_k > lm.max_batch) PF_FAIL(h, "pf_track_frame: bad arguments (top_k %d, landmark max_batch %d)", top_k, lm.max_batch);
     PF_HIP(h, hipSetDevice(h->device));
     if (ensure_track(h, top_k)) return 1;
-    TrackState& t = h->track;
+    TrackPool& P = h->track;
+    TrackSlot& t = P.slots[0];
     // 1. frame upload + frame-difference gate (facer.py:55-63,98-118): one 8-byte read-back decides whether the detector runs
     unsigned long long diff_sum = 0;
     int has_prev = 0;
@@ -86,70 +190,25 @@ static int track_frame_impl(pf_handle* h, const uint8_t* bgr, int mem, int heigh
     const double diff = has_prev ? (double)diff_sum / (double)height / (double)width / 3.0 : 0.0;
     const bool run_det = !has_prev || !t.has_track || diff > (double)diff_thres;
     if (detector_ran) *detector_ran = run_det ? 1 : 0;
-    const unsigned char* d_frame = h->pipe.d_cur;
-    const int rows = det.bufs[det.hdr.out_buf0].elems_per_item / 16;
-    if (ensure_pipeline(h, 1, top_k, top_k, rows)) return 1;
+    TrackFrameDesc& d = P.h_desc[0];
+    d.slot = 0; d.cur = t.cur; d.has_track = t.has_track ? 1 : 0;
+    d.lm_valid = (t.lm_valid && !run_det) ? 1 : 0;     // a detector frame drops the smoothing history (facer.py:60)
+    d.det = run_det ? 0 : -1; d.cmp = 0;
     begin_call(h);
-    const double* d_boxes_in = t.d_track_box;      // boxes that enter sort_and_filter
-    const int* d_n_in = t.d_n_track;
-    const int* d_in_f32 = t.d_f32 + 0;             // ... and their dtype flag (k_track.h): track_box's, unless the detector runs
-    if (run_det) {
-        const LetterboxGeom g = letterbox_geom(height, width, det.hdr.in_h, det.hdr.in_w);
-        if (run_detector_stage(h, d_frame, 1, height, width, row_stride, g)) return 1;
-        const float* d_rows = (const float*)det.buf_ptr(det.hdr.out_buf0);
-        if (planted_rows) {   // planted-candidate protocol: the network ran, its rows are replaced
-            if (planted_n != rows) PF_FAIL(h, "pf_track_frame_planted: %d rows, the detector produces %d", planted_n, rows);
-            const size_t bytes = (size_t)rows * 16 * sizeof(float);
-            if (ensure_dev(h, h->pipe.d_rows_planted, h->pipe.rows_planted_bytes, bytes)) return 1;
-            PF_HIP(h, hipMemcpyAsync(h->pipe.d_rows_planted, planted_rows, bytes, hipMemcpyHostToDevice, h->stream));
-            d_rows = h->pipe.d_rows_planted;
-        }
-        if (run_nms_stage(h, d_rows, rows, 1, g, score_thres, nms_iou_thres, 0.f, 1, false)) return 1;
-        JudgeArgs ja{};
-        ja.prev = t.d_track_box; ja.n_prev = t.d_n_track; ja.has_prev = t.has_track ? 1 : 0; ja.prev_f32 = t.d_f32 + 0;
-        ja.now_f32 = h->pipe.d_keep_rows; ja.now_stride = 16; ja.now_f64 = nullptr; ja.now_f32_flag = nullptr; ja.n_now = h->pipe.d_keep_count;
-        ja.out = t.d_judged; ja.n_out = t.d_n_judged; ja.out_f32 = t.d_f32 + 1;
-        ja.iou_thres = track_iou_thres; ja.alpha = smooth_box; ja.max_now = kTrackMaxNow;
-        PF_LAUNCH(track_judge_kernel, dim3(1), dim3(256), h->stream, ja);
-        t.lm_valid = false;                        // trace.previous_landmarks_set = None (facer.py:60)
-        d_boxes_in = t.d_judged;
-        d_n_in = t.d_n_judged;
-        d_in_f32 = t.d_f32 + 1;
-    }
-    // 2. sort_and_filter -> boxes_return (float64 rows, stay on the device)
-    SelectArgs sa{};
-    sa.boxes = d_boxes_in; sa.n = d_n_in; sa.out = t.d_sel; sa.n_out = t.d_n_sel; sa.boxes_f32 = d_in_f32; sa.min_face = min_face; sa.top_k = top_k;
-    PF_LAUNCH(track_select_kernel, dim3(1), dim3(64), h->stream, sa);
-    // 3. landmark stage on the selected boxes (count read on the device: slots >= n_sel are skipped)
-    if (run_landmark_stage(h, d_frame, height, width, row_stride, h->pipe.d_sel_boxes, t.d_n_sel, top_k, top_k, t.d_sel, d_in_f32)) return 1;
-    // 4. One-Euro smoothing against the previous sets + hull boxes
-    const int nxt = t.cur ^ 1;
-    PF_LAUNCH(track_count_kernel, dim3(1), dim3(64), h->stream, (const int*)h->pipe.d_crop_params, (const int*)t.d_n_sel, t.d_n_lm[nxt]);
-    GroupTrackArgs ga{};
-    ga.kps = h->pipe.d_kps; ga.scores_in = (const float*)lm.buf_ptr(lm.hdr.out_buf1); ga.crop_params = h->pipe.d_crop_params;
-    ga.n_sel = t.d_n_sel;
-    ga.prev_lm = t.d_lm[t.cur]; ga.prev_dx = t.d_dx[t.cur]; ga.n_prev = t.d_n_lm[t.cur]; ga.prev_valid = t.lm_valid ? 1 : 0;
-    ga.prev_f32 = t.d_f32 + 2 + t.cur; ga.out_f32 = t.d_f32 + 2 + nxt;
-    static const int one = 1;     // the new sets are float32 (the network's landmarks) unless a face is smoothed against the previous ones
-    PF_HIP(h, hipMemcpyAsync(t.d_f32 + 2 + nxt, &one, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    ga.out_lm = t.d_lm[nxt]; ga.out_dx = t.d_dx[nxt]; ga.n_out = t.d_n_lm[nxt];
-    ga.hull = t.d_hull; ga.scores_out = t.d_scores;
-    ga.iou_thres = track_iou_thres; ga.scale_w = (double)width; ga.scale_h = (double)height;
-    ga.min_cutoff = 0.15; ga.beta = 0.8; ga.d_cutoff = 1.0;          // OneEuroFilter defaults, lk.py:100-101
-    PF_LAUNCH(track_group_kernel, dim3(top_k), dim3(128), h->stream, ga);
-    // 5. track_box = judge_boxs(boxes_return, hull boxes) (facer.py:70-81)
-    JudgeArgs jb{};
-    jb.prev = t.d_sel; jb.n_prev = t.d_n_sel; jb.has_prev = 1; jb.prev_f32 = d_in_f32;
-    jb.now_f32 = nullptr; jb.now_stride = 4; jb.now_f64 = t.d_hull; jb.now_f32_flag = t.d_f32 + 2 + nxt; jb.n_now = t.d_n_lm[nxt];
-    jb.out = t.d_track_box; jb.n_out = t.d_n_track; jb.out_f32 = t.d_f32 + 0;
-    jb.iou_thres = track_iou_thres; jb.alpha = smooth_box; jb.max_now = top_k;
-    PF_LAUNCH(track_judge_kernel, dim3(1), dim3(256), h->stream, jb);
-    t.cur = nxt;
-    t.lm_valid = true;
-    t.has_track = true;
+    static const int det_idx0 = 0;
+    // 2.-5. the stream-batched track path with one stream (frame: the resident one pf_set_frame stored)
+    if (track_enqueue(h, P, 1, top_k, h->pipe.d_cur, height, width, run_det ? 1 : 0, &det_idx0, nullptr,
+                      planted_rows, planted_n, score_thres, nms_iou_thres, min_face, track_iou_thres, smooth_box)) return 1;
     // 6. results of this frame: the only device->host traffic of the call besides the 8-byte gate
     int n = 0;
-    PF_HIP(h, hipMemcpyAsync(&n, t.d_n_track, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    std::vector<double>& hb = P.h_box;
+    std::vector<double>& hk = P.h_lm;
+    std::vector<float>& hs = P.h_scores;
+    hb.resize((size_t)top_k * 4); hk.resize((size_t)top_k * 196); hs.resize((size_t)top_k * 98);
+    PF_HIP(h, hipMemcpyAsync(&n, P.v.out_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    PF_HIP(h, hipMemcpyAsync(hb.data(), P.v.out_box, hb.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PF_HIP(h, hipMemcpyAsync(hk.data(), P.v.out_lm, hk.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PF_HIP(h, hipMemcpyAsync(hs.data(), P.v.scores, hs.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     PF_HIP(h, hipStreamSynchronize(h->stream));
     if (check_numerics(h)) {
         // The range guard poisoned this frame's outputs with NaN, and steps 4-5 above have already folded them into the
@@ -164,10 +223,126 @@ static int track_frame_impl(pf_handle* h, const uint8_t* bgr, int mem, int heigh
     n = std::min(n, top_k);
     *n_out = n;
     if (n > 0) {
-        if (boxes) PF_HIP(h, hipMemcpyAsync(boxes, t.d_track_box, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        if (kps) PF_HIP(h, hipMemcpyAsync(kps, t.d_lm[t.cur], (size_t)n * 196 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        if (scores) PF_HIP(h, hipMemcpyAsync(scores, t.d_scores, (size_t)n * 98 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        PF_HIP(h, hipStreamSynchronize(h->stream));
+        if (boxes) memcpy(boxes, hb.data(), (size_t)n * 4 * sizeof(double));
+        if (kps) memcpy(kps, hk.data(), (size_t)n * 196 * sizeof(double));
+        if (scores) memcpy(scores, hs.data(), (size_t)n * 98 * sizeof(float));
+    }
+    return 0;
+}
+
+// ---- N video streams on one handle (pf_track_streams*) -----------------------------------------------------------------
+
+int pf_track_streams_config(pf_handle* h, int max_streams, int top_k) {
+    if (!h) return 1;
+    if (max_streams < 1 || top_k < 1) PF_FAIL(h, "pf_track_streams_config: bad arguments (max_streams %d, top_k %d)", max_streams, top_k);
+    PF_HIP(h, hipSetDevice(h->device));
+    TrackPool& P = h->streams;
+    if (track_pool_alloc(h, P, max_streams, top_k)) return 1;
+    PF_HIP(h, hipMalloc((void**)&P.d_sums, (size_t)max_streams * sizeof(unsigned long long)));
+    PF_HIP(h, hipMalloc((void**)&P.d_det_idx, (size_t)max_streams * sizeof(int)));
+    P.h_sums.assign(max_streams, 0);
+    P.h_det_idx.assign(max_streams, 0);
+    return 0;
+}
+
+int pf_track_streams_reset(pf_handle* h, int stream_id) {
+    if (!h) return 1;
+    TrackPool& P = h->streams;
+    if (P.S == 0) PF_FAIL(h, "pf_track_streams_reset: no stream pool (call pf_track_streams_config first)");
+    if (stream_id < -1 || stream_id >= P.S) PF_FAIL(h, "pf_track_streams_reset: stream %d outside [-1, %d)", stream_id, P.S);
+    for (int s = 0; s < P.S; ++s)
+        if (stream_id < 0 || s == stream_id) { TrackSlot& t = P.slots[s]; t.has_track = t.lm_valid = t.have_prev = false; }
+    return 0;
+}
+
+int pf_track_streams(pf_handle* h, int n, const int* stream_ids, const uint8_t* frames, int mem, int height, int width,
+                     const float* det_rows, int rows, float score_thres, float nms_iou_thres, float min_face,
+                     float track_iou_thres, float smooth_box, float diff_thres,
+                     int* counts, double* boxes, double* kps, float* scores, int* detector_ran) {
+    if (!h) return 1;
+    TrackPool& P = h->streams;
+    // every check before anything changes: a rejected call leaves every stream as it was
+    if (P.S == 0) PF_FAIL(h, "pf_track_streams: no stream pool (call pf_track_streams_config first)");
+    Program& det = h->prog[PF_NET_DETECTOR];
+    Program& lm = h->prog[PF_NET_LANDMARK];
+    if (!det.loaded || !lm.loaded) PF_FAIL(h, "pf_track_streams: detector and landmark programs must be loaded");
+    if (n < 1 || !stream_ids || !frames || !counts || height < 1 || width < 1 || (mem != PF_MEM_HOST && mem != PF_MEM_DEVICE))
+        PF_FAIL(h, "pf_track_streams: bad arguments");
+    if (n > P.S) PF_FAIL(h, "pf_track_streams: %d frames exceed max_streams %d", n, P.S);
+    const int K = P.K;
+    if (n * K > lm.max_batch) PF_FAIL(h, "pf_track_streams: %d frames x top_k %d exceed the landmark program's max_batch %d", n, K, lm.max_batch);
+    if (n > det.max_batch) PF_FAIL(h, "pf_track_streams: %d frames exceed the detector program's max_batch %d", n, det.max_batch);
+    const int det_nrows = det.bufs[det.hdr.out_buf0].elems_per_item / 16;
+    if (det_rows && rows != det_nrows) PF_FAIL(h, "pf_track_streams: %d planted rows, the detector produces %d", rows, det_nrows);
+    {
+        std::vector<char> seen(P.S, 0);
+        for (int i = 0; i < n; ++i) {
+            const int s = stream_ids[i];
+            if (s < 0 || s >= P.S) PF_FAIL(h, "pf_track_streams: stream id %d outside [0, %d)", s, P.S);
+            if (seen[s]) PF_FAIL(h, "pf_track_streams: stream id %d listed twice", s);
+            seen[s] = 1;
+        }
+    }
+    const size_t bytes = (size_t)height * width * 3;
+    PF_HIP(h, hipSetDevice(h->device));
+    if (ensure_stream_frames(h, P, bytes)) return 1;
+    if (ensure_pipeline(h, n, n * K, K, det_nrows)) return 1;
+    const unsigned char* d_frames = nullptr;
+    if (stage_frames(h, frames, mem, (size_t)n * bytes, &d_frames)) return 1;
+    // 1. gate fused with the store of the frames into their slots; one read-back of the n sums
+    for (int i = 0; i < n; ++i) {
+        const TrackSlot& t = P.slots[stream_ids[i]];
+        TrackFrameDesc& d = P.h_desc[i];
+        d.slot = stream_ids[i]; d.cur = t.cur; d.has_track = t.has_track ? 1 : 0; d.lm_valid = t.lm_valid ? 1 : 0;
+        d.det = -1; d.cmp = (t.have_prev && t.prev_h == height && t.prev_w == width) ? 1 : 0;
+    }
+    PF_HIP(h, hipMemcpyAsync(P.d_desc, P.h_desc.data(), (size_t)n * sizeof(TrackFrameDesc), hipMemcpyHostToDevice, h->stream));
+    PF_HIP(h, hipMemsetAsync(P.d_sums, 0, (size_t)n * sizeof(unsigned long long), h->stream));
+    GateArgs ga{};
+    ga.cur = d_frames; ga.prev = P.d_frames; ga.bytes = bytes; ga.slot_bytes = P.frame_slot_bytes; ga.desc = P.d_desc; ga.sums = P.d_sums;
+    ga.vec = (bytes % 16 == 0 && ((uintptr_t)d_frames % 16) == 0 && P.frame_slot_bytes % 16 == 0) ? 1 : 0;
+    const size_t words = ga.vec ? bytes / 16 : bytes;
+    const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>(4096, (words + 256 * 16 - 1) / (256 * 16)));
+    if ((words + (size_t)blocks * 256 - 1) / ((size_t)blocks * 256) > PF_GATE_MAX_WORDS) PF_FAIL(h, "pf_track_streams: frame of %zu bytes too large for the gate", bytes);
+    {
+        ProfScope ps(h, "track_gate");
+        PF_LAUNCH(track_gate_kernel, dim3(blocks, n), dim3(256), h->stream, ga);
+    }
+    PF_HIP(h, hipMemcpyAsync(P.h_sums.data(), P.d_sums, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    PF_HIP(h, hipStreamSynchronize(h->stream));
+    // 2. the reference's rule per stream (facer.py:55-63); the slots now hold this call's frames
+    int n_det = 0;
+    for (int i = 0; i < n; ++i) {
+        TrackFrameDesc& d = P.h_desc[i];
+        TrackSlot& t = P.slots[d.slot];
+        const double diff = d.cmp ? (double)P.h_sums[i] / (double)height / (double)width / 3.0 : 0.0;
+        const bool run_det = !d.cmp || !t.has_track || diff > (double)diff_thres;
+        if (detector_ran) detector_ran[i] = run_det ? 1 : 0;
+        if (run_det) { P.h_det_idx[n_det] = i; d.det = n_det++; d.lm_valid = 0; }
+        t.have_prev = true; t.prev_h = height; t.prev_w = width;
+    }
+    const int* d_det_idx = nullptr;                   // identity when every frame runs the detector
+    if (n_det > 0 && n_det < n) {
+        PF_HIP(h, hipMemcpyAsync(P.d_det_idx, P.h_det_idx.data(), (size_t)n_det * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        d_det_idx = P.d_det_idx;
+    }
+    begin_call(h);
+    // 3.-5. detector on the detector frames only, track kernels and landmark stage over all n streams
+    if (track_enqueue(h, P, n, K, d_frames, height, width, n_det, P.h_det_idx.data(), d_det_idx, det_rows, rows,
+                      score_thres, nms_iou_thres, min_face, track_iou_thres, smooth_box)) return 1;
+    // 6. results: one batch of copies, one synchronisation
+    PF_HIP(h, hipMemcpyAsync(counts, P.v.out_count, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (boxes) PF_HIP(h, hipMemcpyAsync(boxes, P.v.out_box, (size_t)n * K * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (kps) PF_HIP(h, hipMemcpyAsync(kps, P.v.out_lm, (size_t)n * K * 196 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (scores) PF_HIP(h, hipMemcpyAsync(scores, P.v.scores, (size_t)n * K * 98 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    PF_HIP(h, hipStreamSynchronize(h->stream));
+    if (check_numerics(h)) {
+        // as in track_frame_impl: the poisoned outputs are already in the state of every stream of this call; those streams
+        // start afresh (no track, no previous frame), the others keep theirs.  The error still names the program slot.
+        const std::string why = h->err;
+        for (int i = 0; i < n; ++i) { TrackSlot& t = P.slots[stream_ids[i]]; t.has_track = t.lm_valid = t.have_prev = false; }
+        h->err = why;
+        return 1;
     }
     return 0;
 }

@@ -66,6 +66,17 @@ int pf_load_program(pf_handle* h, int slot, const void* blob, size_t bytes, int 
 int pf_landmark_forward(pf_handle* h, const void* input, int input_kind, int mem, int batch,
                         float* loc_fix, float* score, int out_mem);
 
+/* Face attributes of the landmark network's fc head (Net.fc, model.py:269,286-293), for landmark programs built with
+ * face_attrs=True: copies `rows` rows [rows][7] left by the handle's last pf_landmark_forward (rows = batch),
+ * pf_landmarks* (box order; rows whose valid flag is 0 are left untouched), pf_run_frames* ([F][top_k], like kps),
+ * pf_track_frame* (the n_out tracked faces, compacted like kps) or pf_track_streams ([n][top_k], compacted like kps).
+ * raw = 1: Net.forward's x (x[0:3] head pose / 90, x[3:7] face-state logits); raw = 0: pose in degrees (90 x[0:3], about
+ * x, y, z as cv2.decomposeProjectionMatrix returns them) then sigmoid(x[3:7]) = P(eye of points 60-67 closed), P(eye of
+ * points 68-75 closed), P(mouth closed), P(mouth wide open).  Enqueued on the handle's stream (out_mem = PF_MEM_DEVICE)
+ * or copied and synchronised (host memory).  Fails with a message when the program has no head, when the handle's last
+ * call left no rows or when more rows are asked than it left. */
+int pf_face_attrs(pf_handle* h, int rows, float* out, int raw, int out_mem);
+
 /* Detector forward == session.run of yolov5n-0.5.onnx (face_detector.py:29-31):
  * input float32 NCHW [1][3][384][640] RGB/255 or uint8 NHWC letterboxed RGB;
  * output [rows][16] decoded rows (cx,cy,w,h,obj,10 landmark coords,cls), rows = 15120 at 384x640. */
@@ -276,6 +287,10 @@ int pf_batch_sync(pf_batch* b);
 int pf_batch_run_frames(pf_batch* b, const uint8_t* frames, int mem, int n_frames, int height, int width,
                         const float* det_rows, int rows, float score_thres, float iou_thres, float min_face, int top_k,
                         int* counts, float* boxes, float* kps, float* scores, int out_mem);
+
+/* pf_face_attrs of the lanes, gathered: the [n_frames][top_k][7] attribute rows of the last pf_batch_run_frames (front mode
+ * on or off), laid out like its kps.  Device output is enqueued on the lanes' streams. */
+int pf_batch_face_attrs(pf_batch* b, int rows, float* out, int raw, int out_mem);
 
 /* Engine options.  PF_OPT_HIP_GRAPH = 1: pf_run_frames* calls whose buffers all live on the device are captured
  * into a hipGraph per distinct (pointers, shapes, thresholds) and replayed (launch-latency bound small batches). */

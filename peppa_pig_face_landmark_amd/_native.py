@@ -46,6 +46,11 @@ def _declare(lib):
     lib.pf_landmark_forward.argtypes = [vp, vp, i, i, i, vp, vp, i]
     lib.pf_detector_forward.argtypes = [vp, vp, i, i, i, vp, i]
     lib.pf_read_tensor.argtypes = [vp, i, i, i, fp, sz]
+    if hasattr(lib, "pf_face_attrs"):      # absent from builds that predate it (tools/compare_libs.py loads those too)
+        lib.pf_face_attrs.argtypes = [vp, i, vp, i, i]
+        lib.pf_face_attrs.restype = i
+        lib.pf_batch_face_attrs.argtypes = [vp, i, vp, i, i]
+        lib.pf_batch_face_attrs.restype = i
     lib.pf_detect.argtypes = [vp, vp, i, i, i, i, f, f, fp, i, ip]
     lib.pf_landmarks.argtypes = [vp, vp, i, i, i, i, fp, i, fp, fp, ip]
     lib.pf_landmarks_f64.argtypes = [vp, vp, i, i, i, i, C.POINTER(C.c_double), i, fp, fp, ip]
@@ -261,8 +266,9 @@ class Engine:
         return buf.raw[:n.value], float(ms.value)
 
     # ---- network seams ------------------------------------------------------------------------
-    def landmark_forward(self, x: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-        """x: uint8 [B,S,S,3] or float32 [B,3,S,S] -> (loc_fix [B,196], score [B,98])."""
+    def landmark_forward(self, x: np.ndarray, attrs: bool = False):
+        """x: uint8 [B,S,S,3] or float32 [B,3,S,S] -> (loc_fix [B,196], score [B,98]).  ``attrs=True`` (a program built with
+        ``face_attrs=True``): + the raw fc-head output [B,7] of the same faces (``face_attrs(B, raw=True)``)."""
         if x.dtype == np.uint8:
             kind, batch = PF_INPUT_U8_NHWC, x.shape[0]
         elif x.dtype == np.float32:
@@ -274,7 +280,21 @@ class Engine:
         score = np.empty((batch, 98), np.float32)
         self._check(self.lib.pf_landmark_forward(self.h, _ptr(x), kind, PF_MEM_HOST, batch, _ptr(loc), _ptr(score),
                                                  PF_MEM_HOST), "pf_landmark_forward")
+        if attrs:
+            return loc, score, self.face_attrs(batch, raw=True)
         return loc, score
+
+    def face_attrs(self, rows: int, raw: bool = False) -> np.ndarray:
+        """Face attributes [rows, 7] of the faces of the handle's last pf_landmark_forward / pf_landmarks / pf_run_frames /
+        pf_track_frame / pf_track_streams call, in that call's row order (include/peppa_hip.h pf_face_attrs).  raw=True: Net's x (pose / 90, four logits); raw=False: pose in degrees
+        (about x, y, z) then P(eye 60-67 closed), P(eye 68-75 closed), P(mouth closed), P(mouth wide open)."""
+        out = np.zeros((int(rows), 7), np.float32)
+        self._check(self.lib.pf_face_attrs(self.h, int(rows), _ptr(out), 1 if raw else 0, PF_MEM_HOST), "pf_face_attrs")
+        return out
+
+    def face_attrs_device(self, rows: int, d_out: int, raw: bool = False):
+        """Same into device memory, enqueued on the handle's stream."""
+        self._check(self.lib.pf_face_attrs(self.h, int(rows), _ptr(d_out), 1 if raw else 0, PF_MEM_DEVICE), "pf_face_attrs")
 
     def landmark_forward_device(self, d_input: int, kind: int, batch: int, d_loc: int = 0, d_score: int = 0):
         """Same on device pointers (bench): nothing crosses PCIe."""
@@ -732,6 +752,17 @@ class BatchEngine:
                                           min_face, top_k, _ptr(counts), _ptr(boxes), _ptr(kps), _ptr(scores), PF_MEM_HOST)
         self._check(rc, "pf_batch_run_frames")
         return counts, boxes, kps, scores
+
+    def face_attrs(self, rows: int, raw: bool = False) -> np.ndarray:
+        """Face attributes [rows, 7] of the last run_frames* call, laid out like its kps ([F * top_k]; include/peppa_hip.h
+        pf_batch_face_attrs)."""
+        out = np.zeros((int(rows), 7), np.float32)
+        self._check(self.lib.pf_batch_face_attrs(self.b, int(rows), _ptr(out), 1 if raw else 0, PF_MEM_HOST), "pf_batch_face_attrs")
+        return out
+
+    def face_attrs_device(self, rows: int, d_out: int, raw: bool = False):
+        """Same into device memory, enqueued on the lanes' streams."""
+        self._check(self.lib.pf_batch_face_attrs(self.b, int(rows), _ptr(d_out), 1 if raw else 0, PF_MEM_DEVICE), "pf_batch_face_attrs")
 
     def close(self):
         self._host.close()

@@ -26,10 +26,14 @@ from .hip_model_base import _RANGE_ERR
 
 class FrameBatchRunner:
     def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, lanes: int = 3, frames_per_lane: int = 32,
-                 device: Optional[int] = None, library: Optional[str] = None, graph: bool = True, top_k: Optional[int] = None):
+                 device: Optional[int] = None, library: Optional[str] = None, graph: bool = True, top_k: Optional[int] = None,
+                 face_attributes: Optional[bool] = None):
+        """``face_attributes`` (default: ``Engine.face_attributes`` of Skps.yml): every result dict also gets ``"pose"`` and
+        ``"attrs"`` as in ``FaceAna``."""
         cfg = cfg or get_cfg()
         sk = cfg["Skps"]
         eng_cfg = sk.get("Engine", {})
+        self.face_attributes = bool(eng_cfg.get("face_attributes", False)) if face_attributes is None else bool(face_attributes)
         self.device = int(eng_cfg.get("device", 0)) if device is None else int(device)
         self.dtype = eng_cfg.get("dtype", "f32s")
         root = pathlib.Path(__file__).resolve().parents[2]
@@ -63,9 +67,9 @@ class FrameBatchRunner:
         else:
             if self._arch == "teacher":
                 from ...graph.teacher import build_teacher_program
-                blob, _ = build_teacher_program(self._kps_w, self._kps_size, dtype)
+                blob, _ = build_teacher_program(self._kps_w, self._kps_size, dtype, face_attrs=self.face_attributes)
             else:
-                blob, _ = build_student_program(self._kps_w, self._kps_size, dtype)
+                blob, _ = build_student_program(self._kps_w, self._kps_size, dtype, face_attrs=self.face_attributes)
             self.engine.load_program(slot, blob, self.frames_per_lane * self.top_k)
 
     def _guarded(self, fn, *args, **kw):
@@ -92,6 +96,10 @@ class FrameBatchRunner:
             raise ValueError("%d frames exceed lanes * frames_per_lane = %d" % (frames.shape[0], self.max_frames))
         return self._guarded(self.engine.run_frames, frames, self.score_thrs, self.iou_thrs, self.min_face, self.top_k, planted_rows)
 
+    def _run_with_attrs(self, frames, planted_rows=None):
+        r = self.engine.run_frames(frames, self.score_thrs, self.iou_thrs, self.min_face, self.top_k, planted_rows)
+        return r + (self.engine.face_attrs(r[0].shape[0] * self.top_k).reshape(r[0].shape[0], self.top_k, 7),)
+
     def _returned_boxes(self, det_boxes: np.ndarray, kps: np.ndarray) -> np.ndarray:
         """The 'box' a fresh ``FaceAna.run`` hands back (facer.py:81-84): not the detector's box but the hull of the face's
         landmarks, EMA-smoothed against the first detector box it overlaps (``judge_boxs(boxes_return, hulls)``)."""
@@ -112,11 +120,22 @@ class FrameBatchRunner:
         frames = np.stack(frames) if isinstance(frames, (list, tuple)) else np.asarray(frames)
         out: List[List[Dict[str, np.ndarray]]] = []
         for s in range(0, frames.shape[0], self.max_frames):
-            counts, boxes, kps, scores = self.run_arrays(frames[s:s + self.max_frames])
+            chunk = frames[s:s + self.max_frames]
+            if self.face_attributes:
+                if chunk.ndim != 4 or chunk.shape[-1] != 3 or chunk.dtype != np.uint8:
+                    raise ValueError("frames must be uint8 [F,H,W,3]")
+                counts, boxes, kps, scores, attrs = self._guarded(self._run_with_attrs, chunk)
+            else:
+                counts, boxes, kps, scores = self.run_arrays(chunk)
             for f in range(counts.shape[0]):
                 n = int(counts[f])
                 ret = self._returned_boxes(boxes[f, :n], kps[f, :n]) if n else np.zeros((0, 4), np.float32)
-                out.append([{"box": ret[i], "kps": kps[f, i], "scores": scores[f, i], "det_box": boxes[f, i]} for i in range(n)])
+                res = [{"box": ret[i], "kps": kps[f, i], "scores": scores[f, i], "det_box": boxes[f, i]} for i in range(n)]
+                if self.face_attributes:        # per-frame network output, not smoothed
+                    for i, d in enumerate(res):
+                        d["pose"] = attrs[f, i, :3].copy()
+                        d["attrs"] = attrs[f, i, 3:7].copy()
+                out.append(res)
         return out
 
     def close(self):

@@ -76,7 +76,12 @@ def _box_iou(a, b) -> float:
 
 class FaceAna:
     def __init__(self, verbose: bool = False, cfg: Optional[dict] = None, weights: Optional[dict] = None,
-                 device: Optional[int] = None, library: Optional[str] = None):
+                 device: Optional[int] = None, library: Optional[str] = None, face_attributes: Optional[bool] = None):
+        """``face_attributes`` (default: ``Engine.face_attributes`` of Skps.yml, false): every result dict also gets ``"pose"``
+        (float32 [3], head pose in degrees about x, y, z -- the per-frame network output, not smoothed) and ``"attrs"`` (float32 [4],
+        P(eye of points 60-67 closed), P(eye of points 68-75 closed), P(mouth closed), P(mouth wide open)) from the landmark network's
+        fc head, in both tracking modes.  Needs weights with ``fc.weight`` / ``fc.bias`` (a .pth checkpoint or an .npz made from one,
+        not the ONNX file)."""
         if verbose:
             logger.setLevel(logging.DEBUG)
         cfg = cfg or get_cfg()
@@ -93,13 +98,15 @@ class FaceAna:
         # Engine.device_tracking: keep track_box / previous landmarks / One-Euro state on the GPU (pf_track_frame) instead of
         # walking the boxes through numpy between the two networks on every frame
         self.device_tracking = bool(eng_cfg.get("device_tracking", False))
+        self.face_attributes = bool(eng_cfg.get("face_attributes", False)) if face_attributes is None else bool(face_attributes)
         self._planted_rows = None    # test instrument: callable returning decoded detector rows that replace the detector's own
         self._det_cfg = sk["Detect"]
         self.top_k = sk["Detect"]["topk"]
         self.engine = _native.Engine(dev, library)      # one GPU, one stream, shared by both stages
         max_faces = max(int(eng_cfg.get("max_faces", 8)), int(self.top_k))
         self.face_detector = FaceDetector(sk["Detect"], det_w, engine=self.engine, dtype=dtype)
-        self.face_landmark = FaceLandmark(sk["Keypoints"], kps_w, engine=self.engine, dtype=dtype, max_batch=max_faces)
+        self.face_landmark = FaceLandmark(sk["Keypoints"], kps_w, engine=self.engine, dtype=dtype, max_batch=max_faces,
+                                          face_attributes=self.face_attributes)
         self.trace = GroupTrack(sk["Trace"])
         logger.info("model init done!")
 
@@ -118,13 +125,19 @@ class FaceAna:
         # landmark stage; the frame-difference gate (facer.py:98-118) is evaluated on the GPU against the
         # previous resident frame (exact integer sum, same decision as the numpy code in diff_frames()).
         if self.device_tracking:
-            boxes, kps, scores, _ = run_guarded(
-                [self.face_detector.model, self.face_landmark.model], self.engine.track_frame, image, float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]),
+            fn = self.engine.track_frame
+            if self.face_attributes:
+                def fn(*args):       # the attribute rows of the tracked faces, compacted like kps (pf_face_attrs after pf_track_frame)
+                    r = self.engine.track_frame(*args)
+                    return r + (self.engine.face_attrs(len(r[0])),)
+            out = run_guarded(
+                [self.face_detector.model, self.face_landmark.model], fn, image, float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]),
                 float(self.min_face), int(self.top_k), float(self.iou_thres), float(self.alpha), float(self.diff_thres),
                 self._planted_rows() if self._planted_rows is not None else None)
+            boxes, kps, scores = out[:3]
             self.previous_image = image
             self.track_box = boxes
-            return self.to_dict(boxes, kps, scores)
+            return self.to_dict(boxes, kps, scores, out[4] if self.face_attributes else None)
         diff = self.engine.set_frame(image)
         self.previous_image = image
         if diff is None or self.track_box is None or diff > self.diff_thres:
@@ -135,11 +148,15 @@ class FaceAna:
             boxes = self.track_box
         boxes = self.sort_and_filter(boxes)
         boxes_return = np.array(boxes)
-        landmarks, states = self.face_landmark(None, boxes)
+        attrs = None
+        if self.face_attributes:
+            landmarks, states, attrs = self.face_landmark(None, boxes)
+        else:
+            landmarks, states = self.face_landmark(None, boxes)
         landmarks = self.trace.calculate(image, landmarks)
         hulls = [[np.min(l[:, 0]), np.min(l[:, 1]), np.max(l[:, 0]), np.max(l[:, 1])] for l in landmarks]
         self.track_box = self.judge_boxs(boxes_return, np.array(hulls))
-        return self.to_dict(self.track_box, landmarks, states)
+        return self.to_dict(self.track_box, landmarks, states, attrs)
 
     def imread(self, path_or_bytes, want_host: bool = True):
         """``cv2.imread(path)`` of the reference's demo (demo.py:76) for baseline JPEG files: the Huffman stream is decoded on
@@ -165,8 +182,13 @@ class FaceAna:
                 logger.warning("imread: %s", e)
             return frame
 
-    def to_dict(self, bboxes, kps, states):
-        return [{"box": bboxes[i], "kps": kps[i], "scores": states[i]} for i in range(len(bboxes))]
+    def to_dict(self, bboxes, kps, states, attrs=None):
+        out = [{"box": bboxes[i], "kps": kps[i], "scores": states[i]} for i in range(len(bboxes))]
+        if attrs is not None:
+            for i, d in enumerate(out):
+                d["pose"] = np.asarray(attrs[i, :3], np.float32).copy()
+                d["attrs"] = np.asarray(attrs[i, 3:7], np.float32).copy()
+        return out
 
     def diff_frames(self, previous_frame, image) -> bool:
         """True -> run the detector (facer.py:98-118): mean absolute difference of the frames > 5."""

@@ -48,9 +48,10 @@ class HIPEngine:
 
     def __init__(self, weights: Dict[str, np.ndarray], kind: str, input_shape, device: int = 0, dtype: str = "f32",
                  max_batch: int = 8, engine: Optional[_native.Engine] = None, library: Optional[str] = None,
-                 arch: str = "student"):
+                 arch: str = "student", face_attrs: bool = False):
         if kind not in ("keypoints", "detector"):
             raise ValueError(kind)
+        self.face_attrs = bool(face_attrs) and kind == "keypoints"    # + the fc head (graph/student.py build_decoder_and_head)
         self.kind = kind
         self.engine = engine if engine is not None else _native.Engine(device, library)
         self.slot = _native.PF_NET_LANDMARK if kind == "keypoints" else _native.PF_NET_DETECTOR
@@ -64,9 +65,9 @@ class HIPEngine:
     def _load(self, dtype: str):
         if self.kind == "keypoints" and self.arch == "teacher":
             from ...graph.teacher import build_teacher_program
-            blob, self.info = build_teacher_program(self._weights, int(self._input_shape[0]), dtype)
+            blob, self.info = build_teacher_program(self._weights, int(self._input_shape[0]), dtype, face_attrs=self.face_attrs)
         elif self.kind == "keypoints":
-            blob, self.info = build_student_program(self._weights, int(self._input_shape[0]), dtype)
+            blob, self.info = build_student_program(self._weights, int(self._input_shape[0]), dtype, face_attrs=self.face_attrs)
         else:
             blob, self.info = build_detector_program(self._weights, (int(self._input_shape[0]), int(self._input_shape[1])), dtype)
         self.dtype = dtype

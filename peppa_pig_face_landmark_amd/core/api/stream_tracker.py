@@ -22,7 +22,10 @@ from .hip_model_base import HIPEngine, run_guarded
 
 class StreamTracker:
     def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, max_streams: int = 8,
-                 device: Optional[int] = None, library: Optional[str] = None, verbose: bool = False):
+                 device: Optional[int] = None, library: Optional[str] = None, verbose: bool = False,
+                 face_attributes: Optional[bool] = None):
+        """``face_attributes`` (default: ``Engine.face_attributes`` of Skps.yml): every result dict also gets ``"pose"`` and
+        ``"attrs"`` as in ``FaceAna`` (per-frame network output, not smoothed)."""
         if verbose:
             logger.setLevel(logging.DEBUG)
         if int(max_streams) < 1:
@@ -38,6 +41,7 @@ class StreamTracker:
         kps_arch = str(sk["Keypoints"].get("model", "student"))
         kps_w = weights.get("keypoints") or _load_weights(root, sk["Keypoints"]["model_path"], "teacher" if kps_arch == "teacher" else "keypoints")
 
+        self.face_attributes = bool(eng_cfg.get("face_attributes", False)) if face_attributes is None else bool(face_attributes)
         self.max_streams = int(max_streams)
         self.top_k = int(sk["Detect"]["topk"])
         self._det_cfg = sk["Detect"]
@@ -51,7 +55,8 @@ class StreamTracker:
         self.detector = HIPEngine(det_w, "detector", sk["Detect"]["input_shape"], dtype=dtype, max_batch=self.max_streams,
                                   engine=self.engine)
         self.landmark = HIPEngine(kps_w, "keypoints", sk["Keypoints"]["input_shape"], dtype=dtype,
-                                  max_batch=self.max_streams * self.top_k, engine=self.engine, arch=kps_arch)
+                                  max_batch=self.max_streams * self.top_k, engine=self.engine, arch=kps_arch,
+                                  face_attrs=self.face_attributes)
         self.engine.track_streams_config(self.max_streams, self.top_k)
         self.last_detector_ran: Dict[int, bool] = {}
         logger.info("stream tracker init done (%d streams)", self.max_streams)
@@ -63,15 +68,28 @@ class StreamTracker:
         ids = [int(s) for s in frames]
         batch = np.stack([np.ascontiguousarray(frames[s]) for s in frames])
         planted = self._planted_rows(ids, batch) if self._planted_rows is not None else None
-        res = run_guarded([self.detector, self.landmark], self.engine.track_streams, ids, batch,
-                          float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]), float(self.min_face),
-                          float(self.iou_thres), float(self.alpha), float(self.diff_thres), planted)
+        K = self.top_k
+
+        def call(*args):
+            r = self.engine.track_streams(*args)
+            if not self.face_attributes:
+                return r, None
+            attrs = self.engine.face_attrs(len(r) * K)           # [n][top_k] rows, compacted like kps
+            return r, [attrs[i * K:i * K + len(b)] for i, (b, _, _, _) in enumerate(r)]
+        res, attrs = run_guarded([self.detector, self.landmark], call, ids, batch,
+                                 float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]), float(self.min_face),
+                                 float(self.iou_thres), float(self.alpha), float(self.diff_thres), planted)
         self.last_detector_ran = {s: ran for s, (_, _, _, ran) in zip(ids, res)}   # did the gate run the detector
-        return {s: self.to_dict(b, k, sc) for s, (b, k, sc, _) in zip(ids, res)}
+        return {s: self.to_dict(b, k, sc, attrs[i] if attrs is not None else None) for i, (s, (b, k, sc, _)) in enumerate(zip(ids, res))}
 
     @staticmethod
-    def to_dict(bboxes, kps, states):
-        return [{"box": bboxes[i], "kps": kps[i], "scores": states[i]} for i in range(len(bboxes))]
+    def to_dict(bboxes, kps, states, attrs=None):
+        out = [{"box": bboxes[i], "kps": kps[i], "scores": states[i]} for i in range(len(bboxes))]
+        if attrs is not None:
+            for i, d in enumerate(out):
+                d["pose"] = np.asarray(attrs[i, :3], np.float32).copy()
+                d["attrs"] = np.asarray(attrs[i, 3:7], np.float32).copy()
+        return out
 
     def reset(self, stream_id: Optional[int] = None):
         """FaceAna.reset() of one stream, or of every stream (None)."""

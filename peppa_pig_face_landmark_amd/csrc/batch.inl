@@ -36,6 +36,8 @@ struct pf_batch {
     hipEvent_t ev_front[2] = {nullptr, nullptr};
     std::vector<hipEvent_t> ev_lane[2];      // lane i's tail of the last call of that parity
     bool ev_lane_live[2] = {false, false};
+    // the last successful pf_batch_run_frames (pf_batch_face_attrs): frames and top_k; lane i holds the records of its slice
+    int attr_frames = 0, attr_top_k = 0;
 };
 
 #define PF_BFAIL(b, ...)                                  \
@@ -274,6 +276,8 @@ int pf_batch_run_frames(pf_batch* b, const uint8_t* frames, int mem, int n_frame
     }
     // every lane's share is checked BEFORE anything is enqueued: a lane that refuses its slice must not leave the lanes in front of
     // it writing into buffers the caller frees when the call fails
+    b->attr_frames = 0;
+    for (pf_handle* h : b->lane) h->attr_kind = 0;
     const Program& fdet = b->front->prog[PF_NET_DETECTOR];
     const bool front = b->front_mode && (mem & 0xff) == PF_MEM_DEVICE && (fdet.loaded ? n_frames <= fdet.max_batch : det_rows != nullptr);
     for (int i = 0; i < L; ++i) {
@@ -308,12 +312,32 @@ int pf_batch_run_frames(pf_batch* b, const uint8_t* frames, int mem, int n_frame
             return 1;
         }
     }
+    for (int i = 0; i < L; ++i) {       // face-attribute rows: lane i holds [its frames][top_k] (enqueued, like the other outputs)
+        const int nf = std::min(per, n_frames - i * per);
+        if (nf <= 0) break;
+        b->lane[i]->attr_kind = 1; b->lane[i]->attr_rows = nf * top_k;
+    }
+    b->attr_frames = n_frames; b->attr_top_k = top_k;
     if (out_mem != PF_MEM_HOST) return 0;
     if (pf_batch_sync(b)) return 1;
     if (counts) memcpy(counts, s_counts, (size_t)n_frames * sizeof(int));
     if (boxes) memcpy(boxes, s_boxes, (size_t)n_frames * n_box * sizeof(float));
     if (kps) memcpy(kps, s_kps, (size_t)n_frames * n_kps * sizeof(float));
     if (scores) memcpy(scores, s_scores, (size_t)n_frames * n_sc * sizeof(float));
+    return 0;
+}
+
+int pf_batch_face_attrs(pf_batch* b, int rows, float* out, int raw, int out_mem) {
+    if (!b) return 1;
+    if (b->attr_frames == 0) PF_BFAIL(b, "pf_batch_face_attrs: no pf_batch_run_frames call has left face-attribute rows");
+    const int L = (int)b->lane.size(), K = b->attr_top_k;
+    if (!out || rows < 0 || rows > b->attr_frames * K) PF_BFAIL(b, "pf_batch_face_attrs: %d rows asked, the last call left %d", rows, b->attr_frames * K);
+    const int per = (b->attr_frames + L - 1) / L;
+    for (int i = 0; i < L; ++i) {       // lane i's rows are rows [i * per * K, ...) of the call: the slices of pf_batch_run_frames
+        const int r0 = i * per * K, nr = std::min(rows - r0, std::min(per, b->attr_frames - i * per) * K);
+        if (nr <= 0) break;
+        if (pf_face_attrs(b->lane[i], nr, out + (size_t)r0 * 7, raw, out_mem)) PF_BFAIL(b, "lane %d: %s", i, pf_last_error(b->lane[i]));
+    }
     return 0;
 }
 

@@ -114,6 +114,15 @@ struct pf_handle {
     void* comm = nullptr;
     unsigned char comm_id[128] = {0};
     int comm_rank = -1, comm_world = 0;
+    // rows of face-attribute records the last landmark-running call left (pf_face_attrs): kind 0 = none, 1 = rows 0 .. attr_rows-1 of
+    // the landmark program's out_buf2 as they are (pf_landmark_forward, pf_run_frames*), 2 = the same with the valid flags of
+    // pf_landmarks (snapshot in h_attr_valid / d_attr_valid, taken by that call), 3 = rows of attr_src (the tracking calls: records
+    // compacted like their scores by track_group_kernel into d_track_attrs)
+    int attr_kind = 0, attr_rows = 0;
+    const float* attr_src = nullptr;
+    std::vector<int> h_attr_valid;
+    int* d_attr_valid = nullptr; size_t attr_valid_bytes = 0;
+    float* d_track_attrs = nullptr; size_t track_attrs_bytes = 0;
     // profiling
     bool profiling = false;
     std::map<std::string, ProfEntry> prof;
@@ -230,6 +239,7 @@ static int launch_conv(pf_handle* h, const Program& p, const PfOpRec& op, int B,
     memcpy(&a.acc_scale, &f[22], 4);
     a.dbg = h->dbg;
     a.range_slot = range_slot;
+    a.gap_parts = f[24] > 0 ? (float*)p.buf_ptr(f[24] - 1) : nullptr;
     // tile configurations: index -> (BM pixels, BN channels).  The channel tile is chosen so that
     // q tiles of NT*16 channels cover Npad with the least padding (NT <= 8), ties -> fewer tiles.
     static const int bm[PF_CONV_NCFG] = {128, 128, 256, 256, 128, 128, 128, 256, 128};
@@ -283,6 +293,13 @@ static int launch_conv(pf_handle* h, const Program& p, const PfOpRec& op, int B,
             // k_hero.h loads all 128 channels of every pixel as 16-byte vectors, unmasked: a 3x3 conv whose inC < Cpad == 128 would feed
             // neighbouring bytes to the MFMAs and the range guard -- such a layer takes the masked halo kernel below
             const bool hero = a.Npad == 128 && a.Cpad == 128 && a.inC == 128 && (a.inLd & 3) == 0 && a.outW == 64;
+            if (a.gap_parts) {          // + per-tile channel sums of the output (the face-attribute head's decx4 pool; ir.py conv(gap_parts=True))
+                if (hero && f[23] == 2) PF_LAUNCH((conv3x3_hero_kernel<4, true, true, true>), grid, dim3(512), h->stream, a);
+                else if (hero) PF_LAUNCH((conv3x3_hero_kernel<4, true, false, true>), grid, dim3(512), h->stream, a);
+                else if (a.Npad == 128) PF_LAUNCH((conv3x3_halo_split_kernel<128, 4, 2, 128, true>), grid, dim3(512), h->stream, a);
+                else PF_FAIL(h, "conv: per-tile channel sums need 128 output channels (Npad %d)", a.Npad);
+                return 0;
+            }
             if (hero && (host_dbg(h) & 16384)) PF_LAUNCH((conv3x3_hero_kernel<4, false>), grid, dim3(512), h->stream, a);   // A/B aid (ablation build)
             else if (hero && f[23] == 2) PF_LAUNCH((conv3x3_hero_kernel<4, true, true>), grid, dim3(512), h->stream, a);   // ONE f16 product (opt-in per conv)
             else if (hero && !(host_dbg(h) & 2048)) PF_LAUNCH((conv3x3_hero_kernel<4>), grid, dim3(512), h->stream, a);   // k_hero.h
@@ -297,6 +314,7 @@ static int launch_conv(pf_handle* h, const Program& p, const PfOpRec& op, int B,
             return 0;
         }
     }
+    if (a.gap_parts) PF_FAIL(h, "conv: per-tile channel sums are produced by the split-precision 3x3 kernels with 128 outputs only");
     // heat-map score head: bias-only arg-max epilogue (nothing stored, tiles never straddle a face)
     if (SPLIT && use_split && pointwise && cfg == 0 && a.amax_val && !a.store_out && !a.res && !a.fbias && !a.gate && a.act == PF_ACT_NONE &&
         (M % 128) == 0) {
@@ -1027,8 +1045,35 @@ static int run_program_t(pf_handle* h, int slot, const void* d_input, int input_
                 const int lpp = ti.C / VE;
                 if (lpp < 1 || lpp > 64 || (lpp & (lpp - 1))) PF_FAIL(h, "scse: C/VE=%d must be a power of two <= 64", lpp);
                 const long long total = (long long)B * a.HW;
+                if (f[5] > 0) {        // + per-tile channel sums (the face-attribute head's decx8 pool; ir.py scse(gap_parts=True))
+                    if (lpp != 64 || (a.HW % PF_SCSE_TILE) != 0) PF_FAIL(h, "scse: tile sums need C/VE == 64 and HW %% %d == 0", PF_SCSE_TILE);
+                    ProfScope ps(h, "scse_sum");
+                    PF_LAUNCH((scse_tile_sum_kernel<T>), dim3((unsigned)(B * (a.HW / PF_SCSE_TILE))), dim3(256), h->stream, a,
+                              (float*)p.buf_ptr(f[5] - 1));
+                    break;
+                }
                 ProfScope ps(h, "scse");
                 PF_LAUNCH((scse_kernel<T>), dim3((unsigned)((total + 256 / lpp - 1) / (256 / lpp))), dim3(256), h->stream, a);
+                break;
+            }
+            case PF_OP_FACEATTR: {
+                FaceAttrsArgs a{};
+                a.out = (float*)p.buf_ptr(f[0]); a.wt = (const float*)p.cptr(f[1]); a.bias = (const float*)p.cptr(f[2]);
+                a.B = B;
+                int k = 0;
+                for (int s = 0; s < 3; ++s) {
+                    const int32_t* g = f + 3 + 5 * s;
+                    a.src[s].p = (const float*)p.buf_ptr(g[0]);
+                    a.src[s].nparts = g[1]; a.src[s].C = g[2]; a.src[s].ld = g[3];
+                    memcpy(&a.src[s].scale, &g[4], 4);
+                    if (g[1] < 1 || g[2] < 1 || g[3] < g[2] || (long long)g[1] * g[3] > p.bufs[g[0]].elems_per_item)
+                        PF_FAIL(h, "face_attrs: bad pooled source %d", s);
+                    k += g[2];
+                }
+                if (k != PF_FACE_ATTR_K || p.bufs[f[0]].elems_per_item < PF_FACE_ATTR_REC)
+                    PF_FAIL(h, "face_attrs: pooled vector of %d channels (the fc head takes %d)", k, PF_FACE_ATTR_K);
+                ProfScope ps(h, "face_attrs");
+                PF_LAUNCH(face_attrs_kernel, dim3(B), dim3(256), h->stream, a);
                 break;
             }
             case PF_OP_HMDEC: {
@@ -1139,6 +1184,7 @@ static int run_program_t(pf_handle* h, int slot, const void* d_input, int input_
         v.poison0 = (float*)p.buf_ptr(p.hdr.out_buf0); v.n0 = (long long)B * p.bufs[p.hdr.out_buf0].elems_per_item;
         if (p.hdr.out_buf1 >= 0 && p.hdr.out_buf1 != p.hdr.out_buf0) { v.poison1 = (float*)p.buf_ptr(p.hdr.out_buf1); v.n1 = (long long)B * p.bufs[p.hdr.out_buf1].elems_per_item; }
         if (h->pipe.d_kps_for_decode) { v.poison2 = h->pipe.d_kps_for_decode; v.n2 = (long long)B * 98 * 2; }
+        if (p.hdr.out_buf2 >= 0) { v.poison3 = (float*)p.buf_ptr(p.hdr.out_buf2); v.n3 = (long long)B * p.bufs[p.hdr.out_buf2].elems_per_item; }
         PF_LAUNCH(range_verdict_kernel, dim3(v.n_ops), dim3(64), h->stream, v);
     }
     PF_HIP(h, hipGetLastError());
@@ -1248,6 +1294,8 @@ void pf_destroy(pf_handle* h) {
         if (p.d_range) (void)hipFree(p.d_range);
     }
     if (h->d_stage) (void)hipFree(h->d_stage);
+    if (h->d_attr_valid) (void)hipFree(h->d_attr_valid);
+    if (h->d_track_attrs) (void)hipFree(h->d_track_attrs);
     if (h->d_dbg) {
         unsigned long long u[48];
         if (hipMemcpy(u, h->d_dbg + 64, sizeof(u), hipMemcpyDeviceToHost) == hipSuccess) {
@@ -1310,6 +1358,7 @@ int pf_sync(pf_handle* h) {
 int pf_load_program(pf_handle* h, int slot, const void* blob, size_t bytes, int max_batch) {
     if (!h) return 1;
     if (slot < 0 || slot >= PF_NET_SLOTS) PF_FAIL(h, "slot %d out of range", slot);
+    if (slot == PF_NET_LANDMARK) h->attr_kind = 0;       // the records of the previous program are gone with its arena
     if (!blob || bytes < sizeof(PfHeader)) PF_FAIL(h, "program blob too small");
     if (max_batch < 1) PF_FAIL(h, "max_batch must be >= 1");
     PF_HIP(h, hipSetDevice(h->device));
@@ -1396,7 +1445,9 @@ int pf_landmark_forward(pf_handle* h, const void* input, int input_kind, int mem
     h->pipe.d_crop_for_decode = nullptr;
     h->pipe.d_kps_for_decode = nullptr;
     begin_call(h);
+    h->attr_kind = 0;
     if (net_forward_common(h, PF_NET_LANDMARK, input, input_kind, mem, batch, input_kind == PF_INPUT_U8_NHWC ? px : px * 4)) return 1;
+    h->attr_kind = 1; h->attr_rows = batch;
     if (copy_out(h, p.buf_ptr(p.hdr.out_buf0), loc_fix, (size_t)batch * p.buf_item_bytes(p.hdr.out_buf0), out_mem)) return 1;
     if (copy_out(h, p.buf_ptr(p.hdr.out_buf1), score, (size_t)batch * p.buf_item_bytes(p.hdr.out_buf1), out_mem)) return 1;
     if (out_mem == PF_MEM_HOST) {
@@ -1417,6 +1468,41 @@ int pf_detector_forward(pf_handle* h, const void* input, int input_kind, int mem
     if (out_mem == PF_MEM_HOST) {
         PF_HIP(h, hipStreamSynchronize(h->stream));
         return check_numerics(h);
+    }
+    return 0;
+}
+
+int pf_face_attrs(pf_handle* h, int rows, float* out, int raw, int out_mem) {
+    if (!h) return 1;
+    Program& p = h->prog[PF_NET_LANDMARK];
+    if (!p.loaded) PF_FAIL(h, "pf_face_attrs: landmark program not loaded");
+    if (p.hdr.out_buf2 < 0)
+        PF_FAIL(h, "pf_face_attrs: the loaded landmark program has no face-attribute head (build it with face_attrs=True)");
+    if (!out || rows < 0 || (out_mem != PF_MEM_HOST && out_mem != PF_MEM_DEVICE && out_mem != PF_MEM_HOST_PINNED))
+        PF_FAIL(h, "pf_face_attrs: bad arguments");
+    if (h->attr_kind == 0) PF_FAIL(h, "pf_face_attrs: the handle's last call left no face-attribute rows (pf_landmark_forward, "
+                                      "pf_landmarks*, pf_run_frames*, pf_track_frame* and pf_track_streams do)");
+    if (rows > h->attr_rows) PF_FAIL(h, "pf_face_attrs: %d rows asked, the last call left %d", rows, h->attr_rows);
+    if (rows == 0) return 0;
+    PF_HIP(h, hipSetDevice(h->device));
+    FaceAttrsPickArgs a{};
+    a.rec = h->attr_kind == 3 ? h->attr_src : (const float*)p.buf_ptr(p.hdr.out_buf2);
+    a.col0 = raw ? PF_FACE_ATTR_RAW : PF_FACE_ATTR_COOKED;
+    a.valid = h->attr_kind == 2 ? h->d_attr_valid : nullptr; a.rows = rows;
+    if (out_mem == PF_MEM_DEVICE) {
+        a.out = out;
+        PF_LAUNCH(face_attrs_pick_kernel, dim3(pf_div_up(rows * 7, 256)), dim3(256), h->stream, a);
+        PF_HIP(h, hipGetLastError());
+        return 0;
+    }
+    // host memory: the records come over, the picked rows are written on the host (rows whose pf_landmarks valid flag is 0 are left
+    // as they were, like the kps of pf_landmarks)
+    std::vector<float> rec((size_t)rows * PF_FACE_ATTR_REC);
+    PF_HIP(h, hipMemcpyAsync(rec.data(), a.rec, rec.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    PF_HIP(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < rows; ++i) {
+        if (h->attr_kind == 2 && !h->h_attr_valid[i]) continue;
+        memcpy(out + (size_t)i * 7, rec.data() + (size_t)i * PF_FACE_ATTR_REC + a.col0, 7 * sizeof(float));
     }
     return 0;
 }

@@ -61,7 +61,9 @@ struct ConvGemmArgs {
     // first channel chunk only, 128 = no per-tap barrier; conv_gemm_split_kernel: 16 as above, 256 = operands (pixels AND weights)
     // fetched for the first K step only, 512 = no split / LDS store of the pixel operand, 1024 = no depthwise taps in the fused
     // expand + depthwise epilogue.  Tables: profiles/r02_*ablations.md.
-    int dbg;
+    int dbg;    // per-tile channel sums of the stored output (GAPP epilogue instances only, conv_gemm_epilogue): [B][nslots][Npad] f32,
+    // nslots = (OHW / BM) * WARPS_M -- slot = (tile of the face, M-wave); the face-attribute head's pools (k_layers.h face_attrs_kernel)
+    float* gap_parts;
 };
 
 template <typename T> struct ConvMma;
@@ -84,7 +86,14 @@ __device__ __forceinline__ int pf_lds_chunk_off(int row, int chunk) {
 
 // ---- fused epilogue shared by the direct and the split-precision kernels ----------------------
 // acc[j][i][r] = D[channel n0 + wn*WN + 16j + 4*(lane>>4) + r][pixel m0 + wm*WM + 16i + (lane&15)]
-template <typename T, int BM, int BN, int WARPS_M, int WARPS_N>
+//
+// GAPP (compile-time, off in every default instance): the epilogue also leaves the channel sums of exactly the values it stores
+// (after bias, residual and activation) in a.gap_parts[face][slot][Npad], slot = (tile of the face) * WARPS_M + wm.  A lane adds its
+// MT pixels per channel, the 16 lanes of a row (the 16 pixels of a sub-tile) meet by four DPP exchanges, lane 0 of the row stores
+// its four channels as one vector.  Every slot is written by exactly one wave with a plain store and the consumer adds the slots in
+// a fixed order: no atomics, the same bits at any batch size or tile-to-workgroup mapping.  Host guarantees: OHW % BM == 0, so a
+// tile never straddles a face, and Npad % 4 == 0.
+template <typename T, int BM, int BN, int WARPS_M, int WARPS_N, bool GAPP = false>
 __device__ __forceinline__ void conv_gemm_epilogue(const ConvGemmArgs& a, pf_f32x4 (&acc)[BN / WARPS_N / 16][BM / WARPS_M / 16],
                                                    int m0, int n0, int wm, int wn, int lane, int M, int OHW, float acc_scale) {
     constexpr int WM = BM / WARPS_M, WN = BN / WARPS_N;
@@ -122,6 +131,7 @@ __device__ __forceinline__ void conv_gemm_epilogue(const ConvGemmArgs& a, pf_f32
         int best_i[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) { best_v[r] = -3.0e38f; best_i[r] = 0x7fffffff; }
+        float gsum[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             const int m = m0 + wm * WM + i * 16 + pcol;
@@ -146,6 +156,12 @@ __device__ __forceinline__ void conv_gemm_epilogue(const ConvGemmArgs& a, pf_f32
                 }
             }
             pf_act_n<4>(v, a.act);
+            if constexpr (GAPP) {
+                if (mok) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) gsum[r] += v[r];
+                }
+            }
             if (want_amax && mok) {
                 const int local = m - b * OHW;
 #pragma unroll
@@ -173,6 +189,21 @@ __device__ __forceinline__ void conv_gemm_epilogue(const ConvGemmArgs& a, pf_f32
                         else if (n + r < a.outCpad) o[(size_t)(n + r) * a.outCs] = (T)0.f;
                     }
                 }
+            }
+        }
+        if constexpr (GAPP) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                gsum[r] += pf_row_xchg_f32<0>(gsum[r]);
+                gsum[r] += pf_row_xchg_f32<1>(gsum[r]);
+                gsum[r] += pf_row_xchg_f32<2>(gsum[r]);
+                gsum[r] += pf_row_xchg_f32<3>(gsum[r]);
+            }
+            if (pcol == 0 && m0 < M && n + 3 < a.Npad) {
+                const int b = m0 / OHW;
+                const int nslots = (OHW / BM) * WARPS_M;
+                const int slot = ((m0 - b * OHW) / BM) * WARPS_M + wm;
+                *reinterpret_cast<pf_f32x4*>(a.gap_parts + ((size_t)b * nslots + slot) * a.Npad + n) = pf_f32x4{gsum[0], gsum[1], gsum[2], gsum[3]};
             }
         }
         if (want_amax) {
@@ -1312,7 +1343,8 @@ __global__ __launch_bounds__(512, 4) void expdw_image_s2_kernel(ConvGemmArgs a) 
 // per tap (LDS-DMA, two stages).  Activation fetches, conversions and LDS writes drop ~4x (halo overhead 2.06x
 // at W = 64); the matrix-core work and the epilogue are unchanged.  Host guarantees: pad = dil = stride = 1,
 // W in {16, 32, 64}, (H * W) % 128 == 0, no input gate.
-template <int BN, int WARPS_M, int WARPS_N, int BM = 128>
+// GAPP: + the per-tile channel sums of the output (conv_gemm_epilogue; the face-attribute head's decx4 pool at 128 / 64 inputs)
+template <int BN, int WARPS_M, int WARPS_N, int BM = 128, bool GAPP = false>
 __global__ __launch_bounds__(WARPS_M * WARPS_N * 64, WARPS_M * WARPS_N / 2) void conv3x3_halo_split_kernel(ConvGemmArgs a) {
     constexpr int NTHR = WARPS_M * WARPS_N * 64;
     constexpr int WM = BM / WARPS_M, WN = BN / WARPS_N;
@@ -1491,7 +1523,7 @@ __global__ __launch_bounds__(WARPS_M * WARPS_N * 64, WARPS_M * WARPS_N / 2) void
         if (last_tap) { tap = 0; ++cb; } else ++tap;
     }
     pf_amax_commit(a.range_slot, amax, amax_seen);
-    conv_gemm_epilogue<float, BM, BN, WARPS_M, WARPS_N>(a, acc, m0, n0, wm, wn, lane, M, OHW, a.acc_scale);
+    conv_gemm_epilogue<float, BM, BN, WARPS_M, WARPS_N, GAPP>(a, acc, m0, n0, wm, wn, lane, M, OHW, a.acc_scale);
 }
 
 // ---- fused DecoderBlock front end with the low-res patch and its filters resident in LDS ------------------------

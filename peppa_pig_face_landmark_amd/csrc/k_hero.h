@@ -19,7 +19,9 @@
 // rounded to f16, exact products, f32 accumulation -- instead of the three of the split: no lo planes, no lo weight rows in the stream,
 // a third of the MFMAs.  Which layers tolerate it is a property of the network: tools/teacher_precision_study.py --model student
 // (profiles/r06_student_precision_study.txt) puts this conv alone at 4.9e-5 of the oracle's landmarks (north star 1e-3).
-template <int CB, bool LATE_DMA = true, bool ONEPROD = false>
+// GAPP (opt-in, ir.py conv(gap_parts=True)): + the per-tile channel sums of the stored output (conv_gemm_epilogue), the decx4 pool of the
+// face-attribute head.  Off: the kernel is the one it was before the flag existed.
+template <int CB, bool LATE_DMA = true, bool ONEPROD = false, bool GAPP = false>
 __global__ __launch_bounds__(512, 4) void conv3x3_hero_kernel(ConvGemmArgs a) {
     constexpr int BN = 128, BM = 128, W = 64, TR = 2, WARPS_M = 4, WARPS_N = 2, NTHR = 512;
     constexpr int WM = BM / WARPS_M, WN = BN / WARPS_N, MT = WM / 16, NT = WN / 16;
@@ -194,5 +196,5 @@ __global__ __launch_bounds__(512, 4) void conv3x3_hero_kernel(ConvGemmArgs a) {
         pf_sched_fence();
     });
     pf_amax_commit(a.range_slot, amax, amax_seen);
-    conv_gemm_epilogue<float, BM, BN, WARPS_M, WARPS_N>(a, acc, m0, 0, wm, wn, lane, M, OHW, a.acc_scale);
+    conv_gemm_epilogue<float, BM, BN, WARPS_M, WARPS_N, GAPP>(a, acc, m0, 0, wm, wn, lane, M, OHW, a.acc_scale);
 }

@@ -9,6 +9,8 @@
 //   gap_kernel            global average pool -> f32 [B][C]   (SE, cSE, ASPPPooling model.py:49)
 //   fc_kernel             tiny dense layers on pooled vectors (SE / cSE / ASPP pooling branch)
 //   scse_kernel           x*cSE + x*sSE                        (SCSEModule.forward model.py:129-130)
+//   scse_tile_sum_kernel  the same + per-tile channel sums of its output (face-attribute head, decx8 pool)
+//   face_attrs_kernel     the landmark network's fc head (Net.fc, model.py:269,286-293) on partial-sum slabs
 //   hm_decode_kernel      final arg-max reduction + offset gather + landmark un-normalisation
 //                         (COTRAIN.postp model.py:511-554, face_landmark.py:112-113)
 #pragma once
@@ -473,19 +475,12 @@ struct ScseArgs {
     int B, HW, C, ld, outLd;
 };
 
+// one pixel's SCSE output for the VE channels of lane cl (LPP lanes per pixel); shared by scse_kernel and scse_tile_sum_kernel, so the
+// two store the same bits
 template <typename T>
-__global__ __launch_bounds__(256) void scse_kernel(ScseArgs a) {
+__device__ __forceinline__ typename PfVec<T>::type scse_pixel(const ScseArgs& a, long long pp, int b, int cl, int LPP) {
     typedef typename PfVec<T>::type vec_t;
     constexpr int VE = PfVec<T>::N;
-    const int LPP = a.C / VE;  // lanes per pixel: power of two <= 64 (host checks)
-    const int ppb = 256 / LPP;
-    const int t = threadIdx.x;
-    const int cl = t % LPP;
-    const long long pix = (long long)blockIdx.x * ppb + t / LPP;
-    const long long total = (long long)a.B * a.HW;
-    const bool ok = pix < total;
-    const long long pp = ok ? pix : 0;
-    const int b = (int)(pp / a.HW);
     const vec_t x = pf_ldv<T>(static_cast<const T*>(a.in) + (size_t)pp * a.ld + cl * VE);
     float dot = 0.f;
 #pragma unroll
@@ -498,7 +493,59 @@ __global__ __launch_bounds__(256) void scse_kernel(ScseArgs a) {
         const float xv = (float)x[e];
         o[e] = (T)(xv * a.cse[(size_t)b * a.C + cl * VE + e] + xv * sse);
     }
+    return o;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void scse_kernel(ScseArgs a) {
+    constexpr int VE = PfVec<T>::N;
+    const int LPP = a.C / VE;  // lanes per pixel: power of two <= 64 (host checks)
+    const int ppb = 256 / LPP;
+    const int t = threadIdx.x;
+    const int cl = t % LPP;
+    const long long pix = (long long)blockIdx.x * ppb + t / LPP;
+    const long long total = (long long)a.B * a.HW;
+    const bool ok = pix < total;
+    const long long pp = ok ? pix : 0;
+    const int b = (int)(pp / a.HW);
+    const auto o = scse_pixel<T>(a, pp, b, cl, LPP);
     if (ok) pf_stv<T>(static_cast<T*>(a.out) + (size_t)pp * a.outLd + cl * VE, o);
+}
+
+// SCSE + per-tile channel sums of exactly the values it stores (the decx8 pool of the face-attribute head; ir.py scse(gap_parts=True)).
+// A workgroup owns PF_SCSE_TILE consecutive pixels of one face (host: HW % PF_SCSE_TILE == 0, C / VE == 64 lanes per pixel, C <= 512):
+// each wave walks its share of the tile one pixel at a time (the per-pixel arithmetic of scse_kernel), every lane keeping running sums of
+// its VE channels; the four waves' sums meet in LDS and are added in wave order.  parts[face][tile][C]: one plain store per slot (no
+// atomics; the consumer adds the tiles in order), 32 tiles per face at 32 x 32.
+#define PF_SCSE_TILE 32
+template <typename T>
+__global__ __launch_bounds__(256) void scse_tile_sum_kernel(ScseArgs a, float* __restrict__ parts) {
+    constexpr int VE = PfVec<T>::N;
+    constexpr int LPP = 64, WAVES = 4;
+    __shared__ float red[WAVES][LPP * VE];
+    const int t = threadIdx.x, cl = t & 63, w = t >> 6;
+    const int tiles = a.HW / PF_SCSE_TILE;
+    const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
+    const long long p0 = (long long)b * a.HW + (long long)tile * PF_SCSE_TILE;
+    float acc[VE];
+#pragma unroll
+    for (int e = 0; e < VE; ++e) acc[e] = 0.f;
+    for (int q = w; q < PF_SCSE_TILE; q += WAVES) {
+        const long long pp = p0 + q;
+        const auto o = scse_pixel<T>(a, pp, b, cl, LPP);
+        pf_stv<T>(static_cast<T*>(a.out) + (size_t)pp * a.outLd + cl * VE, o);
+#pragma unroll
+        for (int e = 0; e < VE; ++e) acc[e] += (float)o[e];
+    }
+#pragma unroll
+    for (int e = 0; e < VE; ++e) red[w][cl * VE + e] = acc[e];
+    __syncthreads();
+    for (int c = t; c < a.C; c += 256) {
+        float s = red[0][c];
+#pragma unroll
+        for (int q = 1; q < WAVES; ++q) s += red[q][c];
+        parts[((size_t)b * tiles + tile) * a.C + c] = s;
+    }
 }
 
 // --------------------------------------------------------------------------------------------
@@ -902,6 +949,7 @@ struct RangeVerdictArgs {
     float* poison0; long long n0;   // outputs overwritten with NaN on violation (may be null)
     float* poison1; long long n1;
     float* poison2; long long n2;
+    float* poison3; long long n3;   // the face-attribute records (out_buf2) of a program with the fc head
 };
 #define PF_RANGE_TAIL_WORDS 4
 
@@ -955,4 +1003,99 @@ __global__ __launch_bounds__(64) void range_verdict_kernel(RangeVerdictArgs a) {
     for (long long j = t; j < a.n0; j += 64) a.poison0[j] = nan;
     for (long long j = t; j < a.n1; j += 64) a.poison1[j] = nan;
     for (long long j = t; j < a.n2; j += 64) a.poison2[j] = nan;
+    for (long long j = t; j < a.n3; j += 64) a.poison3[j] = nan;
+}
+
+// --------------------------------------------------------------------------------------------
+// The landmark network's second head (Net.forward, model.py:269,286-293): x = fc(cat[gap(decx4) | gap(decx8) | gap(encx16)]), 640 -> 7.
+// x[0:3] is the head pose (cv2.decomposeProjectionMatrix's Euler angles / 90, dataietr.py:302-304), x[3:7] four face-state logits
+// (dataietr.py:306-327).  The pools arrive as partial-sum slabs of the kernels that produced the maps -- conv_gemm_epilogue GAPP
+// (decx4, [B][nparts][ld]), scse_tile_sum_kernel (decx8) -- or as gap_kernel means (nparts = 1, scale = 1).  One workgroup per face:
+//   1. every pooled channel = scale * (sum of its nparts partials in part order; where C divides 256, G = 256 / C thread groups add
+//      contiguous shares of the parts and the G sums are added in group order);
+//   2. wave w computes outputs w and w + 4: lane products over k = lane, lane + 64, ... in order, then an xor-butterfly over the wave;
+//   3. lane 0 writes the record (pf_program.h PF_FACE_ATTR_*): raw x[7], 0, degrees 90 * x[0:3], sigmoid(x[3:7]), 0.
+// Fixed orders everywhere and no atomics: the record's bits do not depend on the batch size or the launch.
+#define PF_FACE_ATTR_K 640
+struct FaceAttrSrc {
+    const float* p;   // [B][nparts][ld]
+    int nparts, C, ld;
+    float scale;
+};
+struct FaceAttrsArgs {
+    FaceAttrSrc src[3];
+    const float* wt;  // [7][640] (Net.fc.weight, row-major as torch stores it)
+    const float* bias;// [7]
+    float* out;       // [B][16]
+    int B;
+};
+
+__global__ __launch_bounds__(256) void face_attrs_kernel(FaceAttrsArgs a) {
+    __shared__ float xs[PF_FACE_ATTR_K];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int b = blockIdx.x;
+    __shared__ float part[256];
+    int c0 = 0;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const FaceAttrSrc& src = a.src[s];
+        const float* base = src.p + (size_t)b * src.nparts * src.ld;
+        // G groups of threads per channel when C divides 256 (decx4: 128 channels, 2 groups): group g adds the parts of its contiguous
+        // share in order, then the groups' sums are added in group order
+        const int G = (src.C <= 256 && (256 % src.C) == 0 && src.nparts > 1) ? 256 / src.C : 1;
+        if (G > 1) {
+            const int c = t % src.C, g = t / src.C;
+            const int chunk = (src.nparts + G - 1) / G, q0 = g * chunk, q1 = min(src.nparts, q0 + chunk);
+            float v = 0.f;
+            for (int q = q0; q < q1; ++q) v += base[(size_t)q * src.ld + c];
+            part[t] = v;
+            __syncthreads();
+            if (t < src.C) {
+                float w = part[t];
+                for (int q = 1; q < G; ++q) w += part[q * src.C + t];
+                xs[c0 + t] = w * src.scale;
+            }
+            __syncthreads();
+        } else {
+            for (int c = t; c < src.C; c += 256) {
+                float v = 0.f;
+                for (int q = 0; q < src.nparts; ++q) v += base[(size_t)q * src.ld + c];
+                xs[c0 + c] = v * src.scale;
+            }
+        }
+        c0 += src.C;
+    }
+    __syncthreads();
+    __shared__ float xr[8];
+    for (int o = w; o < 7; o += 4) {
+        const float* wr = a.wt + (size_t)o * PF_FACE_ATTR_K;
+        float d = 0.f;
+        for (int k = lane; k < PF_FACE_ATTR_K; k += 64) d = fmaf(wr[k], xs[k], d);
+        for (int mask = 32; mask >= 1; mask >>= 1) d += pf_shfl_xor_f32(d, mask);
+        if (lane == 0) xr[o] = d + a.bias[o];
+    }
+    __syncthreads();
+    if (t < 16) {
+        float v = 0.f;
+        if (t < 7) v = xr[t];
+        else if (t >= 8 && t < 11) v = 90.f * xr[t - 8];
+        else if (t >= 11 && t < 15) v = 1.f / (1.f + expf(-xr[t - 8]));
+        a.out[(size_t)b * 16 + t] = v;
+    }
+}
+
+// pf_face_attrs into device memory: out[row][0..7) = record[row][col0 .. col0 + 7); rows whose valid flag (pf_landmarks' snapshot) is 0
+// are left untouched
+struct FaceAttrsPickArgs {
+    const float* rec;   // [rows][PF_FACE_ATTR_REC]
+    const int* valid;   // [rows] or nullptr
+    float* out;         // [rows][7]
+    int rows, col0;
+};
+__global__ __launch_bounds__(256) void face_attrs_pick_kernel(FaceAttrsPickArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.rows * 7) return;
+    const int r = i / 7, c = i - r * 7;
+    if (a.valid && !a.valid[r]) return;
+    a.out[i] = a.rec[(size_t)r * 16 + a.col0 + c];
 }

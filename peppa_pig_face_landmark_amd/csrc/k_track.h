@@ -268,6 +268,8 @@ struct GroupStageArgs {
     const int* crop_params;   // [n][top_k][8]
     double iou_thres, scale_w, scale_h;
     double min_cutoff, beta, d_cutoff;
+    const float* attrs_in;    // [n][top_k][16] face-attribute records of the landmark program (face_attrs=True), or nullptr
+    float* attrs_out;         // [n][top_k][16] the records of the valid faces, compacted like the scores
 };
 struct GroupTrackArgs {       // the operands of one frame
     const float* kps;         // [top_k][98][2] float32 landmarks of this frame (frame coordinates)
@@ -364,6 +366,8 @@ __global__ __launch_bounds__(128) void track_group_kernel(GroupStageArgs g) {
         a.out_dx[(size_t)oi * 196 + 2 * tid] = ddx;
         a.out_dx[(size_t)oi * 196 + 2 * tid + 1] = ddy;
         a.scores_out[(size_t)oi * 98 + tid] = a.scores_in[(size_t)slot * 98 + tid];
+        if (g.attrs_in && tid < 16)
+            g.attrs_out[((size_t)i * K + oi) * 16 + tid] = g.attrs_in[((size_t)i * K + slot) * 16 + tid];
         s_now[2 * tid] = rx;
         s_now[2 * tid + 1] = ry;
     }

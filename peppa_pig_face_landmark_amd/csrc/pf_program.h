@@ -38,11 +38,14 @@ enum PfOpCode : int32_t {
     PF_OP_STEM = 1,     // f: in_t(-1 = program input) out_t wt(u8 input, 1/255 folded) bias act wt(f32 input)
     PF_OP_CONV = 2,     // f: in_t out_t wt bias res_t gate_buf fbias_buf KH KW stride pad dil Cpad Npad N act
                         //    outCs amax_val_buf amax_idx_buf amaxN store_out cfg acc_scale(float bits) use_split
+                        //    gap_parts_buf + 1 (0 = none: per-tile channel sums of the output, [face][(OHW / 128) * 4][Npad]; the hero / halo
+                        //    3x3 kernels with 128 outputs only)
     PF_OP_DW = 3,       // f: in_t out_t wt bias K stride pad dil act
     PF_OP_UPCAT = 4,    // f: lo_t skip_t out_t
     PF_OP_GAP = 5,      // f: in_t out_buf
     PF_OP_FC = 6,       // f: x_buf y_buf wt bias K N act scale2 shift2 act2
-    PF_OP_SCSE = 7,     // f: in_t out_t cse_buf ssew sse_b(float bits)
+    PF_OP_SCSE = 7,     // f: in_t out_t cse_buf ssew sse_b(float bits) gap_parts_buf + 1 (0 = none: per-32-pixel-tile channel sums of the
+                        //    output, [face][HW / 32][C], k_layers.h scse_tile_sum_kernel)
     PF_OP_HMDEC = 8,    // f: val_buf idx_buf feat_t offwt offbias P nslots loc_buf score_buf
     PF_OP_MAXPOOL = 9,  // f: in_t out_t            (2x2 stride 2, ceil mode)
     PF_OP_COPY = 10,    // f: in_t out_t out_cs up  (channel-strided copy, optional nearest x2 upsample)
@@ -78,9 +81,22 @@ enum PfOpCode : int32_t {
                         //    (k_layers.h fc2_kernel: SE gate, cSE gate, ASPP pooled branch); K, R <= 960, R % 4 == 0, N % 4 == 0
     PF_OP_FRONT2 = 26,  // f: out_t w_stem_u8 w_stem_f32 b_stem s_u8 s_f32 (float bits) act_stem w_dw b_dw w_pw b_pw: conv_stem + blocks.0.0 of the Student encoder
                         //    (3x3 s2 3 -> 16 + act, depthwise 3x3 + relu -> 1x1 16 -> 16 + x) in one launch on the program input (k_front2.h); split programs only
+    PF_OP_FACEATTR = 27, // f: out_buf wt bias then per pooled source (3: decx4, decx8, encx16) src_buf nparts C ld scale(float bits): the landmark
+                        //    network's fc head (model.py:269,286-293) on partial-sum slabs / pooled means, one record per face (k_layers.h
+                        //    face_attrs_kernel, record layout PF_FACE_ATTR_* below); programs built with face_attrs=True only
     PF_OP_SEPUP = 12,   // f: lo_t skip_t out_t dwE(lo) dw_b(zeros: folded into pw_bias) pw_wt pw_bias Cpad Npad N act acc_scale(float bits) dw_w(skip) skipx_buf dw_w(lo, plain [9][C1]) dw_v(lo, [4 row classes][9][C1]: vertical interpolation folded in) gap_parts_buf + 1 (0 = none: per-tile channel sums of the output)
                         //    fused bilinear-x2-upsample + concat + depthwise 3x3 + pointwise conv (split kernels)
 };
+
+// Face-attribute record (out_buf2 of a program built with face_attrs=True): 16 f32 per face.
+//   [0, 7)   raw x of Net.forward's first output (model.py:293): x[0:3] head pose / 90, x[3:7] face-state logits
+//   [7]      0
+//   [8, 11)  head pose in degrees, 90 * x[0:3], in cv2.decomposeProjectionMatrix's order (about x, y, z; headpose.py:48-78)
+//   [11, 15) sigmoid(x[3:7]): eye of points 60-67 closed, eye of points 68-75 closed, mouth closed, mouth wide open
+//   [15]     0
+#define PF_FACE_ATTR_REC 16
+#define PF_FACE_ATTR_RAW 0
+#define PF_FACE_ATTR_COOKED 8
 
 // tile configurations of conv_gemm_kernel (index = cfg field)
 #define PF_CONV_NCFG 9

@@ -242,6 +242,7 @@ static int landmarks_impl(pf_handle* h, const uint8_t* bgr, int mem, int height,
         PF_HIP(h, hipMemcpyAsync(h->pipe.d_sel_boxes, boxes, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice, h->stream));
     }
     begin_call(h);
+    h->attr_kind = 0;
     if (run_landmark_stage(h, d_frames, height, width, row_stride, h->pipe.d_sel_boxes, nullptr, n, n, d_b64)) return 1;
     std::vector<int> params((size_t)n * 8);
     std::vector<float> hk((size_t)n * kNumPoints * 2), hs((size_t)n * kNumPoints);
@@ -250,6 +251,12 @@ static int landmarks_impl(pf_handle* h, const uint8_t* bgr, int mem, int height,
     PF_HIP(h, hipMemcpyAsync(hs.data(), lm.buf_ptr(lm.hdr.out_buf1), hs.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     PF_HIP(h, hipStreamSynchronize(h->stream));
     if (check_numerics(h)) return 1;
+    if (lm.hdr.out_buf2 >= 0) {       // pf_face_attrs: the valid flags of THIS call, kept apart from the crop-parameter scratch
+        h->h_attr_valid.resize(n);
+        for (int i = 0; i < n; ++i) h->h_attr_valid[i] = params[(size_t)i * 8] != 0;
+        if (ensure_dev(h, h->d_attr_valid, h->attr_valid_bytes, (size_t)n * sizeof(int))) return 1;
+        PF_HIP(h, hipMemcpy(h->d_attr_valid, h->h_attr_valid.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    }
     for (int i = 0; i < n; ++i) {
         const int ok = params[(size_t)i * 8];
         if (valid) valid[i] = ok;
@@ -257,6 +264,7 @@ static int landmarks_impl(pf_handle* h, const uint8_t* bgr, int mem, int height,
         if (kps) memcpy(kps + (size_t)i * kNumPoints * 2, hk.data() + (size_t)i * kNumPoints * 2, kNumPoints * 2 * sizeof(float));
         if (scores) memcpy(scores + (size_t)i * kNumPoints, hs.data() + (size_t)i * kNumPoints, kNumPoints * sizeof(float));
     }
+    if (lm.hdr.out_buf2 >= 0) { h->attr_kind = 2; h->attr_rows = n; }
     return 0;
 }
 
@@ -392,6 +400,7 @@ int pf_run_frames_planted(pf_handle* h, const uint8_t* frames, int mem, int n_fr
     if (out_mem != PF_MEM_HOST && out_mem != PF_MEM_DEVICE && out_mem != PF_MEM_HOST_PINNED) PF_FAIL(h, "pf_run_frames: bad out_mem %d", out_mem);
     // results into page-locked host memory are plain asynchronous copies on the stream: they capture into the graph too
     begin_call(h);
+    h->attr_kind = 0;
     const bool graphable = h->use_graphs && !h->profiling && mem == PF_MEM_DEVICE &&
                            (out_mem == PF_MEM_DEVICE || out_mem == PF_MEM_HOST_PINNED);
     if (!graphable) {
@@ -399,18 +408,21 @@ int pf_run_frames_planted(pf_handle* h, const uint8_t* frames, int mem, int n_fr
                                top_k, counts, boxes, kps, scores, out_mem)) return 1;
         if (out_mem == PF_MEM_HOST) {
             PF_HIP(h, hipStreamSynchronize(h->stream));
-            return check_numerics(h);
+            if (check_numerics(h)) return 1;
         }
+        h->attr_kind = 1; h->attr_rows = n_frames * top_k;          // rows [F][top_k], like kps (pf_face_attrs)
         return 0;
     }
     GraphKey key{};
     key.p[0] = frames; key.p[1] = det_rows; key.p[2] = counts; key.p[3] = boxes; key.p[4] = kps; key.p[5] = scores;
     key.i[0] = n_frames; key.i[1] = height; key.i[2] = width; key.i[3] = rows; key.i[4] = top_k;
     key.f[0] = score_thres; key.f[1] = iou_thres; key.f[2] = min_face;
-    return graphed_call(h, key, [&]() {
+    if (graphed_call(h, key, [&]() {
         return enqueue_run_frames(h, frames, mem, n_frames, height, width, det_rows, rows, score_thres, iou_thres, min_face,
                                   top_k, counts, boxes, kps, scores, out_mem);
-    });
+    })) return 1;
+    h->attr_kind = 1; h->attr_rows = n_frames * top_k;
+    return 0;
 }
 
 int pf_host_alloc(size_t bytes, void** out) {

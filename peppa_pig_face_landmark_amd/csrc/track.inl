@@ -97,6 +97,10 @@ int track_enqueue(pf_handle* h, TrackPool& P, int n, int top_k, const unsigned c
     ga.kps = h->pipe.d_kps; ga.scores_in = (const float*)lm.buf_ptr(lm.hdr.out_buf1); ga.crop_params = h->pipe.d_crop_params;
     ga.iou_thres = track_iou_thres; ga.scale_w = (double)W; ga.scale_h = (double)H;
     ga.min_cutoff = 0.15; ga.beta = 0.8; ga.d_cutoff = 1.0;          // OneEuroFilter defaults, lk.py:100-101
+    if (lm.hdr.out_buf2 >= 0) {      // face-attribute records follow the compaction of the scores (pf_face_attrs)
+        if (ensure_dev(h, h->d_track_attrs, h->track_attrs_bytes, (size_t)n * top_k * PF_FACE_ATTR_REC * sizeof(float))) return 1;
+        ga.attrs_in = (const float*)lm.buf_ptr(lm.hdr.out_buf2); ga.attrs_out = h->d_track_attrs;
+    }
     PF_LAUNCH(track_group_kernel, dim3(top_k, n), dim3(128), h->stream, ga);
     // 5. track_box = judge_boxs(boxes_return, hull boxes) (facer.py:70-81)
     JudgeStageArgs jb{};
@@ -175,6 +179,7 @@ static int track_frame_impl(pf_handle* h, const uint8_t* bgr, int mem, int heigh
                             float track_iou_thres, float smooth_box, float diff_thres,
                             int* n_out, double* boxes, double* kps, float* scores, int* detector_ran) {
     if (!h) return 1;
+    h->attr_kind = 0;
     Program& det = h->prog[PF_NET_DETECTOR];
     Program& lm = h->prog[PF_NET_LANDMARK];
     if (!det.loaded || !lm.loaded) PF_FAIL(h, "pf_track_frame: detector and landmark programs must be loaded");
@@ -222,6 +227,7 @@ static int track_frame_impl(pf_handle* h, const uint8_t* bgr, int mem, int heigh
     }
     n = std::min(n, top_k);
     *n_out = n;
+    if (lm.hdr.out_buf2 >= 0) { h->attr_kind = 3; h->attr_src = h->d_track_attrs; h->attr_rows = n; }   // rows [n], like kps
     if (n > 0) {
         if (boxes) memcpy(boxes, hb.data(), (size_t)n * 4 * sizeof(double));
         if (kps) memcpy(kps, hk.data(), (size_t)n * 196 * sizeof(double));
@@ -260,6 +266,7 @@ int pf_track_streams(pf_handle* h, int n, const int* stream_ids, const uint8_t* 
                      float track_iou_thres, float smooth_box, float diff_thres,
                      int* counts, double* boxes, double* kps, float* scores, int* detector_ran) {
     if (!h) return 1;
+    h->attr_kind = 0;
     TrackPool& P = h->streams;
     // every check before anything changes: a rejected call leaves every stream as it was
     if (P.S == 0) PF_FAIL(h, "pf_track_streams: no stream pool (call pf_track_streams_config first)");
@@ -344,6 +351,7 @@ int pf_track_streams(pf_handle* h, int n, const int* stream_ids, const uint8_t* 
         h->err = why;
         return 1;
     }
+    if (lm.hdr.out_buf2 >= 0) { h->attr_kind = 3; h->attr_src = h->d_track_attrs; h->attr_rows = n * K; }   // rows [n][K], like kps
     return 0;
 }
 

@@ -28,6 +28,9 @@ OP_STEM, OP_CONV, OP_DW, OP_UPCAT, OP_GAP, OP_FC, OP_SCSE, OP_HMDEC, OP_MAXPOOL,
 OP_MBX = 24
 OP_FC2 = 25
 OP_FRONT2 = 26
+OP_FACEATTR = 27
+FACE_ATTR_REC = 16        # f32 per face of the face-attribute record (csrc/pf_program.h PF_FACE_ATTR_*)
+SCSE_TILE = 32            # pixels per partial sum of scse(gap_parts=True) (csrc/k_layers.h PF_SCSE_TILE)
 
 # conv_gemm_kernel tile configurations (BM, BN, WARPS_M); index == cfg field
 CONV_CFGS = [(128, 128, 2), (128, 64, 2), (256, 32, 4), (256, 16, 4)]
@@ -208,10 +211,14 @@ class ProgramBuilder:
     def conv(self, x: int, weight: np.ndarray, bias: np.ndarray, act: str, *, stride: int = 1, pad: int = 0,
              dil: int = 1, out: Optional[int] = None, res: int = -1, gate_buf: int = -1, fbias_buf: int = -1,
              out_cs: int = 1, amax: Optional[Tuple[int, int, int]] = None, store_out: bool = True,
-             cfg: int = -1, out_name: str = "", products: int = 3) -> int:
+             cfg: int = -1, out_name: str = "", products: int = 3, gap_parts: bool = False):
         """Dense conv as MFMA implicit GEMM.  weight [N,Cin,KH,KW] float (already BN-folded).
         ``products=1`` (split programs, opt-in): ONE f16 product per 32 k instead of the split's three, where the engine has such a
-        kernel for the shape (csrc/k_hero.h; elsewhere the field is ignored and the conv runs at full precision)."""
+        kernel for the shape (csrc/k_hero.h; elsewhere the field is ignored and the conv runs at full precision).
+        ``gap_parts=True`` (only where ``conv_can_sum``): returns (out, parts buffer) -- the kernel also leaves per-tile channel sums of
+        its output, [(OHW / 128) * 4][Npad] f32 per face (csrc/k_conv_gemm.h conv_gemm_epilogue GAPP)."""
+        if gap_parts:
+            assert self.conv_can_sum(x, weight, pad=pad, stride=stride, dil=dil) and out is None and amax is None and gate_buf < 0
         ti = self.tensors[x]
         n, cin, kh, kw = weight.shape
         assert cin == ti.real_c, (cin, ti.real_c)
@@ -227,11 +234,23 @@ class ProgramBuilder:
         b[:n] = bias
         boff = self.const_f32(b)
         av, ai, an = amax if amax is not None else (-1, -1, 0)
-        self._op(OP_CONV, [x, out, woff, boff, res, gate_buf, fbias_buf, kh, kw, stride, pad, dil, cpad, npad, n,
-                           ACT[act], out_cs, av, ai, an, 1 if store_out else 0, cfg,
-                           struct.unpack("<i", struct.pack("<f", acc_scale))[0], (2 if products == 1 else 1) if use_split else 0],
-                 [self._tb(x), self._tb(res), gate_buf, fbias_buf], [self._tb(out), av, ai])
-        return out
+        fields = [x, out, woff, boff, res, gate_buf, fbias_buf, kh, kw, stride, pad, dil, cpad, npad, n,
+                  ACT[act], out_cs, av, ai, an, 1 if store_out else 0, cfg,
+                  struct.unpack("<i", struct.pack("<f", acc_scale))[0], (2 if products == 1 else 1) if use_split else 0]
+        parts = -1
+        if gap_parts:
+            parts = self.buffer((oh * ow // 128) * 4 * npad, ELEM_F32, "conv.gap_parts")
+            fields.append(parts + 1)
+        self._op(OP_CONV, fields, [self._tb(x), self._tb(res), gate_buf, fbias_buf], [self._tb(out), av, ai, parts])
+        return (out, parts) if gap_parts else out
+
+    def conv_can_sum(self, x: int, weight: np.ndarray, *, pad: int = 0, stride: int = 1, dil: int = 1) -> bool:
+        """Will ``conv`` run on a kernel that can leave per-tile channel sums of its output (``gap_parts=True``)?  The split-precision
+        3x3 kernels with 128 outputs and the input patch in LDS (csrc/k_hero.h, conv3x3_halo_split_kernel<128>; engine.cpp launch_conv)."""
+        ti = self.tensors[x]
+        n, cin, kh, kw = weight.shape
+        return bool(self.conv_uses_split(cin, kh * kw) and (kh, kw, stride, pad, dil) == (3, 3, 1, 1, 1) and ti.W in (16, 32, 64)
+                    and (ti.H * ti.W) % 128 == 0 and _round_up(n, 16) == 128)
 
     def dw(self, x: int, weight: np.ndarray, bias: np.ndarray, act: str, *, stride: int = 1, pad: int = 0,
            dil: int = 1, out_name: str = "") -> int:
@@ -872,12 +891,39 @@ class ProgramBuilder:
                  [xbuf], [out])
         return out
 
-    def scse(self, x: int, cse_buf: int, sse_w: np.ndarray, sse_b: float, out_name: str = "") -> int:
+    def scse_can_sum(self, x: int) -> bool:
+        """Can ``scse`` leave per-tile channel sums of its output (csrc/k_layers.h scse_tile_sum_kernel: 64 lanes per pixel)?"""
+        ti = self.tensors[x]
+        return ti.C == 64 * self.ve and (ti.H * ti.W) % SCSE_TILE == 0
+
+    def scse(self, x: int, cse_buf: int, sse_w: np.ndarray, sse_b: float, out_name: str = "", gap_parts: bool = False):
+        """``gap_parts=True`` (only where ``scse_can_sum``): returns (out, parts buffer) -- per-32-pixel-tile channel sums of the output,
+        [HW / 32][C] f32 per face."""
         ti = self.tensors[x]
         out = self.tensor(ti.H, ti.W, ti.C, name=out_name)
         woff = self.const_f32(sse_w.reshape(-1))
         bbits = struct.unpack("<i", struct.pack("<f", float(sse_b)))[0]
-        self._op(OP_SCSE, [x, out, cse_buf, woff, bbits], [self._tb(x), cse_buf], [self._tb(out)])
+        fields = [x, out, cse_buf, woff, bbits]
+        parts = -1
+        if gap_parts:
+            assert self.scse_can_sum(x)
+            parts = self.buffer((ti.H * ti.W // SCSE_TILE) * ti.C, ELEM_F32, "scse.gap_parts")
+            fields.append(parts + 1)
+        self._op(OP_SCSE, fields, [self._tb(x), cse_buf], [self._tb(out), parts])
+        return (out, parts) if gap_parts else out
+
+    def face_attrs(self, sources, weight: np.ndarray, bias: np.ndarray) -> int:
+        """The landmark network's fc head (model.py:269,286-293) on three pooled sources [(buffer, nparts, C, ld, scale)] in the order
+        decx4, decx8, encx16: pooled = scale * (sum of nparts partial vectors of ld floats, first C used).  Returns the record buffer,
+        ``FACE_ATTR_REC`` f32 per face (csrc/pf_program.h)."""
+        assert len(sources) == 3 and sum(c for _, _, c, _, _ in sources) == 640
+        assert weight.shape == (7, 640) and bias.shape == (7,)
+        out = self.buffer(FACE_ATTR_REC, ELEM_F32, "face_attrs", pinned=True)
+        f = [out, self.const_f32(weight.reshape(7, 640)), self.const_f32(bias)]
+        for buf, nparts, c, ld, scale in sources:
+            assert self.bufs[buf].elems == nparts * ld and c <= ld
+            f += [buf, nparts, c, ld, struct.unpack("<i", struct.pack("<f", float(scale)))[0]]
+        self._op(OP_FACEATTR, f, [b for b, *_ in sources], [out])
         return out
 
     def hmdec(self, val_buf: int, idx_buf: int, feat: int, off_w: np.ndarray, off_b: np.ndarray, points: int,

@@ -47,12 +47,41 @@ def _bn(w: Dict[str, np.ndarray], prefix: str) -> Dict[str, np.ndarray]:
     return {k: w[f"{prefix}.{k}"] for k in ("weight", "bias", "running_mean", "running_var")}
 
 
+FC_TENSORS = ("fc.weight", "fc.bias")
+
+
+def check_fc_weights(w: Dict[str, np.ndarray]) -> None:
+    """The fc head's tensors (Net.fc = nn.Linear(640, 7), model.py:269) must be present and shaped for ``face_attrs=True``."""
+    missing = [k for k in FC_TENSORS if k not in w]
+    if missing:
+        raise ValueError("face_attrs=True needs the fc head's tensors %s, which these weights lack (the reference's ONNX export does not "
+                         "contain them: convert_to_onnx.py traces only the heat-map output); import the trainer's .pth checkpoint "
+                         "instead (weights.load_weights(path, arch, keep_fc=True))" % ", ".join(missing))
+    for k, shape in zip(FC_TENSORS, ((7, 640), (7,))):
+        if tuple(np.shape(w[k])) != shape:
+            raise ValueError("%s has shape %s, the fc head needs %s" % (k, tuple(np.shape(w[k])), shape))
+
+
 def build_decoder_and_head(pb: "ir.ProgramBuilder", w: Dict[str, np.ndarray], encx4: int, encx8: int, encx16: int,
-                           input_size: int, keep_all: bool, debug_full_hm: bool, one_product=()):
+                           input_size: int, keep_all: bool, debug_full_hm: bool, one_product=(), face_attrs: bool = False):
     """Decoder (ASPP + two DecoderBlocks, model.py:212-244) + hm head + fused decode; shared by the
-    Student (mobilenetv3 features 24/40/160 ch) and the Teacher (hrnet_w18 features 128/256/512 ch)."""
+    Student (mobilenetv3 features 24/40/160 ch) and the Teacher (hrnet_w18 features 128/256/512 ch).
+
+    ``face_attrs=True`` adds the second head of ``Net`` (model.py:269,286-293): fc(cat[gap(decx4) | gap(decx8) | gap(encx16)]) -> 7, one
+    record per face in ``info["face_attrs"]`` (csrc/pf_program.h PF_FACE_ATTR_*).  Where the kernels allow it the two large maps are never
+    read again to be pooled: the hero / halo 3x3 conv that writes decx4 (up2.conv2) and the SCSE kernel that writes decx8 leave per-tile
+    channel sums of the values they store, and only encx16 (the ASPP output) takes a gap op.  decx4 comes from conv slabs in f32s programs
+    whose up2.conv2 runs on the hero / halo kernel (``ir.conv_can_sum``), decx8 from SCSE tile sums wherever the SCSE has 64 lanes per
+    pixel and HW % 32 == 0 (``ir.scse_can_sum``: f32 and f32s programs at the usual sizes, not f16, whose 256 channels are 32 lanes).
+    Every other pool is a gap op; the arithmetic of the head is the same."""
+    if face_attrs:
+        check_fc_weights(w)
     h16 = input_size // 16
     c16 = pb.tensors[encx16].C
+
+    def pooled_by_gap(x):
+        c = pb.tensors[x].C
+        return (pb.gap(x), 1, c, c, 1.0)
 
     # ---- ASPP (model.py:64-96) ----------------------------------------------------------------
     a = "decoder.aspp"
@@ -69,8 +98,11 @@ def build_decoder_and_head(pb: "ir.ProgramBuilder", w: Dict[str, np.ndarray], en
     fbias = pb.fc_pair(pooled, wp.reshape(64, -1), bp, "relu", wproj[:, 192:256, 0, 0], None, "none",
                        scale2=s_cat[192:256], shift2=t_cat[192:256], act1b="relu")
     x16 = pb.conv(cat, wproj[:, :192], bproj, "relu", fbias_buf=fbias, out_name=f"{a}.out")
+    pool16 = pooled_by_gap(x16) if face_attrs else None       # encx16 of the fc head: 256 KiB per face at 256 x 256, pooled right away
 
     # ---- decoder blocks (model.py:133-196) -------------------------------------------------------
+    pools = {}
+
     def decoder_block(lo, skip, name, second, att):
         wd, bd = ir.fold_bn(w[f"{name}.conv1.0.conv_dw.0.weight"], w[f"{name}.conv1.0.conv_dw.0.bias"],
                             _bn(w, f"{name}.conv1.0.conv_dw.1"))
@@ -92,15 +124,28 @@ def build_decoder_and_head(pb: "ir.ProgramBuilder", w: Dict[str, np.ndarray], en
             x = pb.conv(x, wp, bp, "relu", out_name=f"{name}.pw")
         if second:
             wt, b = ir.fold_bn(w[f"{name}.conv2.0.weight"], w[f"{name}.conv2.0.bias"], _bn(w, f"{name}.conv2.1"))
-            x = pb.conv(x, wt, b, "relu", pad=1, out_name=f"{name}.conv2", products=1 if "hero" in one_product else 3)
+            kw2 = {"out_name": f"{name}.conv2", "products": 1 if "hero" in one_product else 3}
+            if face_attrs and not att and pb.conv_can_sum(x, wt, pad=1):
+                x, parts2 = pb.conv(x, wt, b, "relu", pad=1, gap_parts=True, **kw2)
+                tx = pb.tensors[x]
+                pools[name] = (parts2, (tx.H * tx.W // 128) * 4, tx.C, 128, 1.0 / (tx.H * tx.W))
+            else:
+                x = pb.conv(x, wt, b, "relu", pad=1, **kw2)
         if att:
             w1, w2 = w[f"{name}.attention2.cSE.1.weight"], w[f"{name}.attention2.cSE.3.weight"]
             tx = pb.tensors[x]
             pooled, kw = (parts, {"nparts": tx.H * tx.W // 128, "xscale": 1.0 / (tx.H * tx.W)}) if parts >= 0 else (pb.gap(x), {})
             cse = pb.fc_pair(pooled, w1.reshape(w1.shape[0], -1), w[f"{name}.attention2.cSE.1.bias"], "relu",
                              w2.reshape(w2.shape[0], -1), w[f"{name}.attention2.cSE.3.bias"], "sigmoid", **kw)
-            x = pb.scse(x, cse, w[f"{name}.attention2.sSE.0.weight"], float(w[f"{name}.attention2.sSE.0.bias"][0]),
-                        out_name=f"{name}.scse")
+            sse = (w[f"{name}.attention2.sSE.0.weight"], float(w[f"{name}.attention2.sSE.0.bias"][0]))
+            if face_attrs and pb.scse_can_sum(x):
+                x, parts2 = pb.scse(x, cse, *sse, out_name=f"{name}.scse", gap_parts=True)
+                tx = pb.tensors[x]
+                pools[name] = (parts2, tx.H * tx.W // ir.SCSE_TILE, tx.C, tx.C, 1.0 / (tx.H * tx.W))
+            else:
+                x = pb.scse(x, cse, *sse, out_name=f"{name}.scse")
+        if face_attrs and name not in pools:
+            pools[name] = pooled_by_gap(x)
         return x
 
     decx8 = decoder_block(x16, encx8, "decoder.upsampler1", False, True)
@@ -125,15 +170,26 @@ def build_decoder_and_head(pb: "ir.ProgramBuilder", w: Dict[str, np.ndarray], en
     pb.conv(decx4, hw[:NUM_POINTS], hb[:NUM_POINTS], "none", out=dummy, amax=(val, idx, NUM_POINTS),
             store_out=False, cfg=0, products=1 if "head" in one_product else 3)
     loc, score = pb.hmdec(val, idx, decx4, hw[NUM_POINTS:, :, 0, 0], hb[NUM_POINTS:], NUM_POINTS, nslots)
+    info["face_attrs"] = -1
+    if face_attrs:
+        # ---- fc head (model.py:286-293): fm = cat[fmx4, fmx8, fmx16] -> Linear(640, 7) ------------------------------------------------
+        srcs = [pools["decoder.upsampler2"], pools["decoder.upsampler1"], pool16]
+        info["face_attrs"] = pb.face_attrs(srcs, w["fc.weight"].astype(np.float64), w["fc.bias"].astype(np.float64))
     return loc, score, info
 
 
 def build_student_program(weights: Dict[str, np.ndarray], input_size: int = 256, dtype: str = "f16",
                           keep_all: bool = False, debug_full_hm: bool = False, fuse_mbconv: bool = True,
                           fuse_mbx: Optional[bool] = None, mbx_se: Optional[str] = None, mbx_waves: int = 16, fuse_fc_pairs: bool = True,
-                          fuse_front2: bool = True, one_product=()):
+                          fuse_front2: bool = True, one_product=(), face_attrs: bool = False):
     """Returns (blob: bytes, info: dict).  ``info['tensors']`` maps layer names to tensor ids for
-    ``pf_read_tensor`` (only meaningful with ``keep_all=True``)."""
+    ``pf_read_tensor`` (only meaningful with ``keep_all=True``).
+
+    ``face_attrs=True`` (opt-in; needs ``fc.weight`` / ``fc.bias``, which ONNX-imported weights lack -> ValueError): the program also
+    runs Net's fc head and writes a third output, one record of head pose and four face-state probabilities per face (see
+    ``build_decoder_and_head``; read with ``Engine.face_attrs``).  Every dtype is supported: f32s programs at the sizes where the hero /
+    halo conv runs pool decx4 from its partial sums, f32 and f32s programs pool decx8 from the SCSE tile sums, the rest with gap ops.  The
+    landmarks and scores are the same bits as without the head."""
     assert input_size % 64 == 0, "input size must be a multiple of 64 (heat-map tile = 128 pixels)"
     if fuse_mbx is None:       # the input-stationary block kernels of stages 3-5 (16 x 16 maps at 256 x 256; csrc/k_mbx.h): on with the other fusions
         fuse_mbx = fuse_mbconv     # mbx_se: None = ir.mbx's choice ("store"), or "recompute" / "store" for every SE block (A/B aid)
@@ -229,8 +285,9 @@ def build_student_program(weights: Dict[str, np.ndarray], input_size: int = 256,
     # three -- "hero" = decoder.upsampler2.conv2 (42 % of the dense MACs; alone 4.9e-5 of the oracle's landmarks on the synthetic weights,
     # profiles/r06_student_precision_study.txt), "head" = the 98 score channels of the heat-map conv (7.4e-5 alone; the offsets at the
     # arg-max stay exact f32 in hm_decode)
-    loc, score, info = build_decoder_and_head(pb, w, feats[1], feats[2], feats[5], input_size, keep_all, debug_full_hm, tuple(one_product))
-    blob = pb.finish([loc, score])
+    loc, score, info = build_decoder_and_head(pb, w, feats[1], feats[2], feats[5], input_size, keep_all, debug_full_hm, tuple(one_product),
+                                              face_attrs=face_attrs)
+    blob = pb.finish([loc, score] + ([info["face_attrs"]] if face_attrs else []))
     info.update({"tensors": dict(pb.tensor_names), "input_size": input_size, "dtype": dtype,
                  "n_ops": len(pb.ops), "const_bytes": len(pb.consts)})
     return blob, info

@@ -7,6 +7,7 @@ architecture inventory (``graph/random_init.py::student_param_shapes``, ``graph/
 a checkpoint of a different architecture fails here, loudly, not as garbage landmarks later.
 
     python -m peppa_pig_face_landmark_amd.weights cotrain.pth --out-dir weights/      # writes kps_student.npz [, kps_teacher.npz]
+    python -m peppa_pig_face_landmark_amd.weights cotrain.pth --out-dir weights/ --keep-fc   # ... with the fc head (face attributes)
 """
 from __future__ import annotations
 
@@ -36,8 +37,13 @@ def _to_numpy(v) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(v, dtype=np.float32))
 
 
-def split_cotrain_state_dict(sd: Mapping[str, object]) -> Tuple[Dict[str, np.ndarray], Optional[Dict[str, np.ndarray]]]:
-    """(student, teacher-or-None) from a COTRAIN state_dict; names relative to ``student.`` / ``teacher.``."""
+FC_SHAPES = {"fc.weight": (7, 640), "fc.bias": (7,)}     # Net.fc / TeacherNet.fc = nn.Linear(640, 7) (model.py:269,319)
+
+
+def split_cotrain_state_dict(sd: Mapping[str, object], keep_fc: bool = False) -> Tuple[Dict[str, np.ndarray], Optional[Dict[str, np.ndarray]]]:
+    """(student, teacher-or-None) from a COTRAIN state_dict; names relative to ``student.`` / ``teacher.``.
+    ``keep_fc=True`` (opt-in, for programs built with ``face_attrs=True``): each model's dictionary also carries the fc head
+    (``fc.weight`` (7, 640), ``fc.bias`` (7,)), which must then be present and of those shapes.  By default the head is dropped."""
     from .graph.random_init import student_param_shapes
     from .graph.teacher import teacher_param_shapes
     flat = {}
@@ -49,6 +55,8 @@ def split_cotrain_state_dict(sd: Mapping[str, object]) -> Tuple[Dict[str, np.nda
 
     def take(prefix: str, shapes) -> Optional[Dict[str, np.ndarray]]:
         exp = _expected(shapes)
+        if keep_fc:
+            exp.update(FC_SHAPES)
         have = {k[len(prefix):]: v for k, v in flat.items() if k.startswith(prefix)}
         if not have:
             return None
@@ -61,7 +69,7 @@ def split_cotrain_state_dict(sd: Mapping[str, object]) -> Tuple[Dict[str, np.nda
             if tuple(arr.shape) != shape:
                 raise ValueError("%s%s has shape %s, the architecture needs %s" % (prefix, name, tuple(arr.shape), shape))
             out[name] = arr
-        return out            # tensors the inference graph does not use (e.g. the dead `fc` head) are dropped
+        return out            # tensors the inference graph does not use (the `fc` head unless keep_fc) are dropped
 
     student = take("student.", student_param_shapes())
     if student is None:
@@ -247,23 +255,41 @@ def weights_from_onnx(path: str, arch: str, check_topology: bool = True) -> Dict
     return out
 
 
-def load_weights(path: str, arch: str) -> Dict[str, np.ndarray]:
+def _check_fc(w: Dict[str, np.ndarray], path: str) -> Dict[str, np.ndarray]:
+    missing = sorted(k for k in FC_SHAPES if k not in w)
+    if missing:
+        raise ValueError("%s lacks the fc head's tensors %s (keep_fc=True): import the trainer's .pth checkpoint with keep_fc=True"
+                         % (path, ", ".join(missing)))
+    for k, shape in FC_SHAPES.items():
+        if tuple(np.shape(w[k])) != shape:
+            raise ValueError("%s: %s has shape %s, the fc head needs %s" % (path, k, tuple(np.shape(w[k])), shape))
+    return w
+
+
+def load_weights(path: str, arch: str, keep_fc: bool = False) -> Dict[str, np.ndarray]:
     """One entry point for every weight file ``FaceAna`` accepts as ``model_path``: ``.onnx`` (the reference's own
     files), ``.npz`` (arrays keyed by state_dict names) or a torch checkpoint ``.pth/.pt`` (needs torch; loaded with
-    ``weights_only=True``)."""
+    ``weights_only=True``).  ``keep_fc=True`` (landmark models): the result must carry the fc head (face attributes); an ONNX
+    export never does (convert_to_onnx.py traces only the heat-map output), so that combination is a ValueError."""
     ext = os.path.splitext(path)[1].lower()
+    if keep_fc and arch not in ("student", "keypoints", "teacher"):
+        raise ValueError("keep_fc applies to the landmark models only, not %r" % arch)
     if ext == ".onnx":
+        if keep_fc:
+            raise ValueError("%s: the reference's ONNX export has no fc head (fc.weight, fc.bias); import the trainer's .pth "
+                             "checkpoint for face attributes" % path)
         return weights_from_onnx(path, "student" if arch == "keypoints" else arch)     # 'teacher' and 'detector' pass through
     if ext == ".npz":
         with np.load(path) as z:
-            return {k: z[k] for k in z.files}
+            w = {k: z[k] for k in z.files}
+        return _check_fc(w, path) if keep_fc else w
     if ext in (".pth", ".pt", ".ckpt"):
         import torch
         sd = torch.load(path, map_location="cpu", weights_only=True)
         if isinstance(sd, dict) and "state_dict" in sd and not any(str(k).startswith(("student.", "module.", "model.")) for k in sd):
             sd = sd["state_dict"]
         if arch in ("student", "keypoints", "teacher"):
-            student, teacher = split_cotrain_state_dict(sd)
+            student, teacher = split_cotrain_state_dict(sd, keep_fc=keep_fc)
             return teacher if arch == "teacher" else student
         return detector_state_dict(sd)
     raise ValueError("unsupported weight file %r (expected .onnx, .npz, .pth or .pt)" % path)
@@ -290,13 +316,14 @@ def detector_state_dict(sd: Mapping[str, object]) -> Dict[str, np.ndarray]:
     return out
 
 
-def import_checkpoint(path: str, out_dir: str) -> Dict[str, str]:
-    """``torch.load`` the checkpoint at ``path`` and write ``kps_student.npz`` (and ``kps_teacher.npz``) to out_dir."""
+def import_checkpoint(path: str, out_dir: str, keep_fc: bool = False) -> Dict[str, str]:
+    """``torch.load`` the checkpoint at ``path`` and write ``kps_student.npz`` (and ``kps_teacher.npz``) to out_dir
+    (``keep_fc``: with the fc head, see ``split_cotrain_state_dict``)."""
     import torch
     sd = torch.load(path, map_location="cpu", weights_only=True)
     if isinstance(sd, dict) and "state_dict" in sd and not any(str(k).startswith(("student.", "module.")) for k in sd):
         sd = sd["state_dict"]
-    student, teacher = split_cotrain_state_dict(sd)
+    student, teacher = split_cotrain_state_dict(sd, keep_fc=keep_fc)
     os.makedirs(out_dir, exist_ok=True)
     written = {"student": os.path.join(out_dir, "kps_student.npz")}
     np.savez(written["student"], **student)
@@ -310,5 +337,5 @@ if __name__ == "__main__":
     if len(sys.argv) < 2:
         sys.exit(__doc__)
     out = sys.argv[sys.argv.index("--out-dir") + 1] if "--out-dir" in sys.argv else "."
-    for model, p in import_checkpoint(sys.argv[1], out).items():
+    for model, p in import_checkpoint(sys.argv[1], out, keep_fc="--keep-fc" in sys.argv).items():
         print("%s -> %s" % (model, p))

@@ -1,6 +1,7 @@
 """Program assembler: builds the packed network program executed by ``csrc/engine.cpp``.
 
-The binary layout is defined in ``csrc/pf_program.h`` -- keep both in sync.  numpy only (the
+The binary layout is defined in ``csrc/pf_program.h``; ``OP_LAYOUT`` below repeats its op records field by field and
+``tests/test_program_layout.py`` fails when the two differ.  numpy only (the
 engine side of the boundary never sees torch / onnxruntime).
 
 A program is a straight-line list of fused layer ops over NHWC activation tensors.  BatchNorm is
@@ -24,11 +25,102 @@ DTYPE_F16, DTYPE_F32, DTYPE_F32_SPLIT = 0, 1, 2
 ELEM_ACT, ELEM_F32, ELEM_I32, ELEM_U8 = 0, 1, 2, 3
 ACT = {"none": 0, "relu": 1, "hswish": 2, "silu": 3, "sigmoid": 4, "hsigmoid": 5}
 
-OP_STEM, OP_CONV, OP_DW, OP_UPCAT, OP_GAP, OP_FC, OP_SCSE, OP_HMDEC, OP_MAXPOOL, OP_COPY, OP_DETDEC, OP_SEPUP, OP_ADDUP, OP_MBCONV, OP_EXPDW, OP_CHAIN, OP_BLOCK, OP_DETUNIT, OP_DETC3, OP_DETSTEM, OP_LMFRONT, OP_HRB, OP_FUSEUP = range(1, 24)
+# op codes (csrc/pf_program.h enum PfOpCode)
+OP_STEM = 1
+OP_CONV = 2
+OP_DW = 3
+OP_UPCAT = 4
+OP_GAP = 5
+OP_FC = 6
+OP_SCSE = 7
+OP_HMDEC = 8
+OP_MAXPOOL = 9
+OP_COPY = 10
+OP_DETDEC = 11
+OP_SEPUP = 12
+OP_ADDUP = 13
+OP_MBCONV = 14
+OP_EXPDW = 15
+OP_CHAIN = 16
+OP_BLOCK = 17
+OP_DETUNIT = 18
+OP_DETC3 = 19
+OP_DETSTEM = 20
+OP_HRB = 22
+OP_FUSEUP = 23
 OP_MBX = 24
 OP_FC2 = 25
 OP_FRONT2 = 26
 OP_FACEATTR = 27
+
+# Fields of every op record in wire order: the members of ``struct Pf<Name>Op`` in csrc/pf_program.h, which also says what they
+# mean (tests/test_program_layout.py holds the two against each other).  "name" is an int32 and "name:f" a float, bit-cast by
+# ``ProgramBuilder._op``.  A trailing "?" marks a field that may be left out (0); every other one must be given.  A tuple
+# (name, count, sub-fields) is an array of `count` nested records, given as a list of dicts; records left out are zeros.
+_CONV3 = ("wt", "bias", "acc_scale:f")
+OP_LAYOUT = {
+    OP_STEM: ("in_t", "out_t", "wt_u8", "bias", "act", "wt_f32", "mfma_w_u8", "mfma_w_f32", "s_u8:f", "s_f32:f"),
+    OP_CONV: ("in_t", "out_t", "wt", "bias", "res_t", "gate_buf", "fbias_buf", "KH", "KW", "stride", "pad", "dil", "Cpad", "Npad", "N",
+              "act", "outCs", "amax_val_buf", "amax_idx_buf", "amaxN", "store_out", "cfg", "acc_scale:f", "use_split",
+              "gap_parts_plus1?"),
+    OP_DW: ("in_t", "out_t", "wt", "bias", "K", "stride", "pad", "dil", "act"),
+    OP_UPCAT: ("lo_t", "skip_t", "out_t"),
+    OP_GAP: ("in_t", "out_buf"),
+    OP_FC: ("x_buf", "y_buf", "wt", "bias", "K", "N", "act", "scale2", "shift2", "act2"),
+    OP_SCSE: ("in_t", "out_t", "cse_buf", "sse_w", "sse_b:f", "gap_parts_plus1?"),
+    OP_HMDEC: ("val_buf", "idx_buf", "feat_t", "off_wt", "off_bias", "P", "nslots", "loc_buf", "score_buf"),
+    OP_MAXPOOL: ("in_t", "out_t"),
+    OP_COPY: ("in_t", "out_t", "out_cs", "up"),
+    OP_DETDEC: ("in_t", "rows_buf", "row0", "stride:f", "anchors", "nrows_total"),
+    OP_SEPUP: ("lo_t", "skip_t", "out_t", "dw_e", "dw_b", "pw_wt", "pw_bias", "Cpad", "Npad", "N", "act", "acc_scale:f", "dw_skip",
+               "skipx_buf", "dw_lo", "dw_v", "gap_parts_plus1?"),
+    OP_ADDUP: ("a_t", "b_t", "out_t", "shift", "act"),
+    OP_MBCONV: ("in_t", "out_t", "res_t", "w_exp", "b_exp", "w_dw", "b_dw", "w_pwl", "b_pwl", "K", "stride", "pad", "dil", "act", "MidPad",
+                "KS", "CoutPad", "Cout", "Mid16", "scale_exp:f", "scale_pwl:f", "variant",
+                ("shuffle", 1, ("act_dw", "act_out", "out_cs", "pass_src_t", "pass_dst_t"))),
+    OP_EXPDW: ("in_t", "out_t", "gap_buf", "w_exp", "b_exp", "w_dw", "b_dw", "K", "pad", "dil", "act", "Cpad", "Npad", "N", "acc_scale:f",
+               "stride?"),
+    OP_CHAIN: ("in_t", "out_t", "n_convs", "C", ("convs", 11, _CONV3)),
+    OP_BLOCK: ("in_t", "out_t", "C", ("convs", 2, _CONV3)),
+    OP_DETUNIT: ("in_t", "out_t", "w1", "b1", "wd", "bd", "w2", "b2", "wd1", "bd1", "w3", "b3", "s1:f", "s2:f", "s3:f", "C", "K1", "stride",
+                 "Cin"),
+    OP_DETC3: ("srcA_t", "srcB_t", "out_t", "out2_t", "rows_buf", "wA", "bA", "wB", "bB", "wC", "bC", "wD", "bD", "wE", "bE", "anchors",
+               "sA:f", "sB:f", "sC:f", "sD:f", "sE:f", "det_stride:f", "CIN", "tail", "upA", "row0", "nrows_total"),
+    OP_DETSTEM: ("out_t", "w1_u8", "w1_f32", "b1", "w2a", "b2a", "w2b", "b2b", "w3", "b3", "s1_u8:f", "s1_f32:f", "s2a:f", "s2b:f", "s3:f"),
+    OP_HRB: ("in_t", "out_t", "w1", "b1", "w2", "b2", "w3", "b3", "wd", "bd", "s1:f", "s2:f", "s3:f", "sd:f", "CIN"),
+    OP_FUSEUP: ("y_t", "out_t", "act", "nsrc", ("src", 3, ("src_t", "wt", "bias", "shift")), "C"),
+    OP_MBX: ("in_t", "out_t", "res_t", "gap_buf", "gate_buf", "w1", "ctile", "w2", "b2", "K", "pad", "dil", "act", "KS", "T", "Cout", "Cexp",
+             "scale1:f", "scale2:f", "mode", "waves"),
+    OP_FC2: ("x_buf", "y_buf", "w1", "b1", "K", "R", "act1", "scale2", "shift2", "act1b", "w2", "b2", "N", "act2", "nparts?", "xscale:f?"),
+    OP_FRONT2: ("out_t", "w_u8", "w_f32", "b_stem", "s_u8:f", "s_f32:f", "act_stem", "w_dw", "b_dw", "w_pw", "b_pw"),
+    OP_FACEATTR: ("out_buf", "wt", "bias", ("src", 3, ("src_buf", "nparts", "C", "ld", "scale:f"))),
+}
+
+
+def _pack_fields(layout, values: dict, what: str) -> List[int]:
+    """Named values -> the int32 words of ``layout`` (a tuple as in OP_LAYOUT); refuses unknown and missing names."""
+    values = dict(values)
+    words: List[int] = []
+    for spec in layout:
+        if isinstance(spec, tuple):
+            name, count, sub = spec
+            items = list(values.pop(name, ()))
+            assert len(items) <= count, f"{what}: {len(items)} {name} records, {count} fit"
+            for i in range(count):
+                words += _pack_fields(sub, items[i], f"{what}.{name}[{i}]") if i < len(items) else [0] * len(sub)
+            continue
+        name, optional = (spec[:-1], True) if spec.endswith("?") else (spec, False)
+        name, is_float = (name[:-2], True) if name.endswith(":f") else (name, False)
+        if name not in values:
+            assert optional, f"{what}: field {name} is missing"
+            words.append(0)
+            continue
+        v = values.pop(name)
+        words.append(struct.unpack("<i", struct.pack("<f", float(v)))[0] if is_float else int(v))
+    assert not values, f"{what}: unknown fields {sorted(values)}"
+    return words
+
+
 FACE_ATTR_REC = 16        # f32 per face of the face-attribute record (csrc/pf_program.h PF_FACE_ATTR_*)
 SCSE_TILE = 32            # pixels per partial sum of scse(gap_parts=True) (csrc/k_layers.h PF_SCSE_TILE)
 
@@ -150,8 +242,8 @@ class ProgramBuilder:
     def const_act(self, arr) -> int:
         return self.const(np.asarray(arr, np.float64).astype(self.np_act))
 
-    def _op(self, code: int, fields: Sequence[int], reads: Sequence[int], writes: Sequence[int]):
-        f = [int(v) for v in fields]
+    def _op(self, code: int, reads: Sequence[int], writes: Sequence[int], **fields):
+        f = _pack_fields(OP_LAYOUT[code], fields, f"op {code}")
         assert len(f) <= OP_FIELDS
         f += [0] * (OP_FIELDS - len(f))
         self.ops.append((code, f, [r for r in reads if r is not None and r >= 0],
@@ -171,15 +263,14 @@ class ProgramBuilder:
         off_u8 = self.const_f32(w / 255.0)
         off_f32 = self.const_f32(w)
         off_b = self.const_f32(bias)
-        f = [-1, out, off_u8, off_b, ACT[act], off_f32, -1, -1, 0, 0]
+        mfma = dict(mfma_w_u8=-1, mfma_w_f32=-1, s_u8=0.0, s_f32=0.0)
         if self.split and co in (16, 64) and self.in_w % 4 == 0 and self.in_h % 2 == 0:
             # f32s programs: the same conv as a split-precision MFMA GEMM on the staged image (csrc/k_front.h stem_mfma_kernel)
             ws = self._stem_k_order(weight)
             wu, su = self._split_rows(ws / 255.0)
             wf, sf = self._split_rows(ws)
-            fbits = lambda v: struct.unpack("<i", struct.pack("<f", v))[0]
-            f[6:10] = [self.const(wu), self.const(wf), fbits(su), fbits(sf)]
-        self._op(OP_STEM, f, [], [self._tb(out)])
+            mfma = dict(mfma_w_u8=self.const(wu), mfma_w_f32=self.const(wf), s_u8=su, s_f32=sf)
+        self._op(OP_STEM, [], [self._tb(out)], in_t=-1, out_t=out, wt_u8=off_u8, bias=off_b, act=ACT[act], wt_f32=off_f32, **mfma)
         return out
 
     SPLIT_MIN_CIN = 64       # pointwise convs below this are bandwidth-bound: the exact-f32 direct kernel is as fast
@@ -234,14 +325,12 @@ class ProgramBuilder:
         b[:n] = bias
         boff = self.const_f32(b)
         av, ai, an = amax if amax is not None else (-1, -1, 0)
-        fields = [x, out, woff, boff, res, gate_buf, fbias_buf, kh, kw, stride, pad, dil, cpad, npad, n,
-                  ACT[act], out_cs, av, ai, an, 1 if store_out else 0, cfg,
-                  struct.unpack("<i", struct.pack("<f", acc_scale))[0], (2 if products == 1 else 1) if use_split else 0]
-        parts = -1
-        if gap_parts:
-            parts = self.buffer((oh * ow // 128) * 4 * npad, ELEM_F32, "conv.gap_parts")
-            fields.append(parts + 1)
-        self._op(OP_CONV, fields, [self._tb(x), self._tb(res), gate_buf, fbias_buf], [self._tb(out), av, ai, parts])
+        parts = self.buffer((oh * ow // 128) * 4 * npad, ELEM_F32, "conv.gap_parts") if gap_parts else -1
+        self._op(OP_CONV, [self._tb(x), self._tb(res), gate_buf, fbias_buf], [self._tb(out), av, ai, parts],
+                 in_t=x, out_t=out, wt=woff, bias=boff, res_t=res, gate_buf=gate_buf, fbias_buf=fbias_buf, KH=kh, KW=kw, stride=stride,
+                 pad=pad, dil=dil, Cpad=cpad, Npad=npad, N=n, act=ACT[act], outCs=out_cs, amax_val_buf=av, amax_idx_buf=ai, amaxN=an,
+                 store_out=1 if store_out else 0, cfg=cfg, acc_scale=acc_scale, use_split=(2 if products == 1 else 1) if use_split else 0,
+                 gap_parts_plus1=parts + 1)
         return (out, parts) if gap_parts else out
 
     def conv_can_sum(self, x: int, weight: np.ndarray, *, pad: int = 0, stride: int = 1, dil: int = 1) -> bool:
@@ -263,7 +352,7 @@ class ProgramBuilder:
         out = self.tensor(oh, ow, c, name=out_name)
         woff = self.const_act(np.transpose(weight.astype(np.float64).reshape(c, k * k), (1, 0)))
         boff = self.const_f32(bias)
-        self._op(OP_DW, [x, out, woff, boff, k, stride, pad, dil, ACT[act]], [self._tb(x)], [self._tb(out)])
+        self._op(OP_DW, [self._tb(x)], [self._tb(out)], in_t=x, out_t=out, wt=woff, bias=boff, K=k, stride=stride, pad=pad, dil=dil, act=ACT[act])
         return out
 
     MBCONV_KERNELS = {(2, 1, 2), (1, 1, 2), (2, 2, 5), (1, 3, 5)}   # (stride, Cin/32, Cout/16 max) built in csrc/k_mbconv.h
@@ -321,7 +410,6 @@ class ProgramBuilder:
         oh = (ti.H + 2 * pad - dil * (k - 1) - 1) // stride + 1
         ow = (ti.W + 2 * pad - dil * (k - 1) - 1) // stride + 1
         out = self.tensor(oh, ow, cout, name=out_name)
-        fbits = lambda v: struct.unpack("<i", struct.pack("<f", v))[0]
         mid16, coutp = _round_up(mid, 16), _round_up(cout, 16)
         if (stride, _round_up(cin, 16)) in ((2, 16), (1, 32)) and coutp <= 32:
             # high-resolution blocks: exact-f32 kernel (f32 fragments halve the register footprint; 16-channel steps)
@@ -333,10 +421,10 @@ class ProgramBuilder:
             wp = np.zeros((coutp, mid16)); wp[:cout, :mid] = w_pwl.reshape(cout, mid)
             bp = np.zeros(coutp); bp[:cout] = b_pwl
             se, sp = self._pow2_unscale(we), self._pow2_unscale(wp)
-            self._op(OP_MBCONV, [x, out, res, self._f32_or_presplit(we, se), self.const_f32(be), self.const_f32(wd), self.const_f32(bd),
-                                 self._f32_or_presplit(wp, sp), self.const_f32(bp), k, stride, pad, dil, ACT[act], mid16, cp, coutp, cout,
-                                 mid16, fbits(se), fbits(sp), 1],
-                     [self._tb(x), self._tb(res)], [self._tb(out)])
+            self._op(OP_MBCONV, [self._tb(x), self._tb(res)], [self._tb(out)], in_t=x, out_t=out, res_t=res,
+                     w_exp=self._f32_or_presplit(we, se), b_exp=self.const_f32(be), w_dw=self.const_f32(wd), b_dw=self.const_f32(bd),
+                     w_pwl=self._f32_or_presplit(wp, sp), b_pwl=self.const_f32(bp), K=k, stride=stride, pad=pad, dil=dil, act=ACT[act],
+                     MidPad=mid16, KS=cp, CoutPad=coutp, Cout=cout, Mid16=mid16, scale_exp=se, scale_pwl=sp, variant=1)
             return out
         midp, cp = _round_up(mid, 32), _round_up(cin, 32)
         we = np.zeros((midp, cp)); we[:mid, :cin] = w_exp.reshape(mid, cin)
@@ -347,10 +435,10 @@ class ProgramBuilder:
         bp = np.zeros(coutp); bp[:cout] = b_pwl
         we_s, se = self._split_rows(we)
         wp_s, sp = self._split_rows(wp)
-        self._op(OP_MBCONV, [x, out, res, self.const(we_s), self.const_f32(be), self.const_f32(wd), self.const_f32(bd),
-                             self.const(wp_s), self.const_f32(bp), k, stride, pad, dil, ACT[act], midp, cp // 32, coutp, cout,
-                             mid16, fbits(se), fbits(sp), 0],
-                 [self._tb(x), self._tb(res)], [self._tb(out)])
+        self._op(OP_MBCONV, [self._tb(x), self._tb(res)], [self._tb(out)], in_t=x, out_t=out, res_t=res,
+                 w_exp=self.const(we_s), b_exp=self.const_f32(be), w_dw=self.const_f32(wd), b_dw=self.const_f32(bd),
+                 w_pwl=self.const(wp_s), b_pwl=self.const_f32(bp), K=k, stride=stride, pad=pad, dil=dil, act=ACT[act],
+                 MidPad=midp, KS=cp // 32, CoutPad=coutp, Cout=cout, Mid16=mid16, scale_exp=se, scale_pwl=sp, variant=0)
         return out
 
     def shuffle_unit_supported(self, c: int) -> bool:
@@ -369,11 +457,11 @@ class ProgramBuilder:
         we_s, se = self._split_rows(w1.reshape(c, c).astype(np.float64))
         wp_s, sp = self._split_rows(w2.reshape(c, c).astype(np.float64))
         wd = w_dw.reshape(c, 9).T
-        fbits = lambda v: struct.unpack("<i", struct.pack("<f", v))[0]
-        self._op(OP_MBCONV, [x2, out, -1, self.const(we_s), self.const_f32(b1), self.const_f32(wd), self.const_f32(b_dw),
-                             self.const(wp_s), self.const_f32(b2), 3, 1, 1, 1, ACT[act], c, c // 32, c, c, c, fbits(se), fbits(sp), 3,
-                             ACT["none"], ACT[act], out_cs, pass_src, pass_dst],
-                 [self._tb(x2), self._tb(pass_src)], [self._tb(out), self._tb(pass_dst)])
+        self._op(OP_MBCONV, [self._tb(x2), self._tb(pass_src)], [self._tb(out), self._tb(pass_dst)], in_t=x2, out_t=out, res_t=-1,
+                 w_exp=self.const(we_s), b_exp=self.const_f32(b1), w_dw=self.const_f32(wd), b_dw=self.const_f32(b_dw),
+                 w_pwl=self.const(wp_s), b_pwl=self.const_f32(b2), K=3, stride=1, pad=1, dil=1, act=ACT[act],
+                 MidPad=c, KS=c // 32, CoutPad=c, Cout=c, Mid16=c, scale_exp=se, scale_pwl=sp, variant=3,
+                 shuffle=[dict(act_dw=ACT["none"], act_out=ACT[act], out_cs=out_cs, pass_src_t=pass_src, pass_dst_t=pass_dst)])
         return out
 
     def det_unit_supported(self, c: int, cin: int, stride: int) -> bool:
@@ -394,7 +482,6 @@ class ProgramBuilder:
         cin2 = c if stride == 1 else cin
         k1 = _round_up(cin2, 32)
         assert w1.shape[:2] == (c, cin2) and w2.shape[:2] == (c, c) and w_dw.shape == (c, 1, 3, 3)
-        fbits = lambda v: struct.unpack("<i", struct.pack("<f", v))[0]
 
         def rows(w, k):
             m = np.zeros((w.shape[0], k), np.float64)
@@ -402,19 +489,18 @@ class ProgramBuilder:
             return self._split_rows(m)
         w1s, s1 = rows(w1, k1)
         w2s, s2 = rows(w2, c)
-        f = [x, out, self.const(w1s), self.const_f32(b1), self.const_f32(w_dw.reshape(c, 9).T), self.const_f32(b_dw),
-             self.const(w2s), self.const_f32(b2)]
+        f = dict(in_t=x, out_t=out, w1=self.const(w1s), b1=self.const_f32(b1), wd=self.const_f32(w_dw.reshape(c, 9).T), bd=self.const_f32(b_dw),
+                 w2=self.const(w2s), b2=self.const_f32(b2))
         if stride == 2:
             assert w_dw1.shape == (cin, 1, 3, 3) and w3.shape[:2] == (c, cin)
             wd1 = np.zeros((9, k1)); wd1[:, :cin] = w_dw1.reshape(cin, 9).T
             bd1 = np.zeros(k1); bd1[:cin] = b_dw1
             w3s, s3 = rows(w3, k1)
-            f += [self.const_f32(wd1), self.const_f32(bd1), self.const(w3s), self.const_f32(b3)]
+            f.update(wd1=self.const_f32(wd1), bd1=self.const_f32(bd1), w3=self.const(w3s), b3=self.const_f32(b3))
         else:
             s3 = 1.0
-            f += [-1, -1, -1, -1]
-        f += [fbits(s1), fbits(s2), fbits(s3), c, k1, stride, cin]
-        self._op(OP_DETUNIT, f, [self._tb(x)], [self._tb(out)])
+            f.update(wd1=-1, bd1=-1, w3=-1, b3=-1)
+        self._op(OP_DETUNIT, [self._tb(x)], [self._tb(out)], s1=s1, s2=s2, s3=s3, C=c, K1=k1, stride=stride, Cin=cin, **f)
         return out
 
     def det_stem(self, w1, b1, w2a, b2a, w2b, b2b, w3, b3, out_name: str = "") -> int:
@@ -423,7 +509,6 @@ class ProgramBuilder:
         assert self.split and w1.shape == (16, 3, 3, 3) and w2a.shape[:2] == (8, 16) and w2b.shape == (16, 8, 3, 3) and w3.shape[:2] == (16, 32)
         assert self.in_h % 4 == 0 and self.in_w % 4 == 0
         out = self.tensor(self.in_h // 4, self.in_w // 4, 16, name=out_name)
-        fbits = lambda v: struct.unpack("<i", struct.pack("<f", v))[0]
 
         def rows(w, n, k):
             m = np.zeros((n, k), np.float64)
@@ -436,9 +521,9 @@ class ProgramBuilder:
         wb, sb = rows(np.transpose(w2b.astype(np.float64), (0, 2, 3, 1)).reshape(16, 72), 16, 96)   # k = tap*8 + c
         wc, sc = rows(w3.reshape(16, 32).astype(np.float64), 16, 32)
         b2 = np.zeros(16); b2[:8] = b2a
-        self._op(OP_DETSTEM, [out, self.const(w1u), self.const(w1f), self.const_f32(b1), self.const(wa), self.const_f32(b2), self.const(wb),
-                              self.const_f32(b2b), self.const(wc), self.const_f32(b3), fbits(s1u), fbits(s1f), fbits(sa), fbits(sb), fbits(sc)],
-                 [], [self._tb(out)])
+        self._op(OP_DETSTEM, [], [self._tb(out)], out_t=out, w1_u8=self.const(w1u), w1_f32=self.const(w1f), b1=self.const_f32(b1),
+                 w2a=self.const(wa), b2a=self.const_f32(b2), w2b=self.const(wb), b2b=self.const_f32(b2b), w3=self.const(wc), b3=self.const_f32(b3),
+                 s1_u8=s1u, s1_f32=s1f, s2a=sa, s2b=sb, s3=sc)
         return out
 
     def hr_bottleneck_supported(self, x: int, mid: int, cout: int, has_ds: bool) -> bool:
@@ -454,21 +539,18 @@ class ProgramBuilder:
         assert self.hr_bottleneck_supported(x, mid, cout, wd is not None)
         assert w1.shape[:2] == (mid, cin) and w2.shape == (mid, mid, 3, 3) and w3.shape[:2] == (cout, mid)
         out = self.tensor(ti.H, ti.W, cout, name=out_name)
-        fbits = lambda v: struct.unpack("<i", struct.pack("<f", v))[0]
         w1s, s1 = self._split_rows(w1.reshape(mid, cin).astype(np.float64))
         w2off, npad, cpad, s2, _ = self.pack_conv_weight(w2, force_split=True)
         assert (npad, cpad) == (64, 64)
         w3s, s3 = self._split_rows(w3.reshape(cout, mid).astype(np.float64))
-        f = [x, out, self.const(w1s), self.const_f32(b1), w2off, self.const_f32(b2), self.const(w3s), self.const_f32(b3)]
+        f = dict(in_t=x, out_t=out, w1=self.const(w1s), b1=self.const_f32(b1), w2=w2off, b2=self.const_f32(b2), w3=self.const(w3s),
+                 b3=self.const_f32(b3), wd=-1, bd=-1)
         sd = 1.0
         if wd is not None:
             assert wd.shape[:2] == (cout, cin)
             wds, sd = self._split_rows(wd.reshape(cout, cin).astype(np.float64))
-            f += [self.const(wds), self.const_f32(bd)]
-        else:
-            f += [-1, -1]
-        f += [fbits(s1), fbits(s2), fbits(s3), fbits(sd), cin]
-        self._op(OP_HRB, f, [self._tb(x)], [self._tb(out)])
+            f.update(wd=self.const(wds), bd=self.const_f32(bd))
+        self._op(OP_HRB, [self._tb(x)], [self._tb(out)], s1=s1, s2=s2, s3=s3, sd=sd, CIN=cin, **f)
         return out
 
     @staticmethod
@@ -491,13 +573,12 @@ class ProgramBuilder:
         assert self.front2_supported()
         assert w_stem.shape == (16, 3, 3, 3) and w_dw.shape == (16, 1, 3, 3) and w_pw.shape[:2] == (16, 16)
         out = self.tensor(self.in_h // 2, self.in_w // 2, 16, name=out_name)
-        fbits = lambda v: struct.unpack("<i", struct.pack("<f", v))[0]
         ws = self._stem_k_order(w_stem)
         wu, su = self._split_rows(ws / 255.0)
         wf, sf = self._split_rows(ws)
-        self._op(OP_FRONT2, [out, self.const(wu), self.const(wf), self.const_f32(b_stem), fbits(su), fbits(sf), ACT[act_stem],
-                             self.const_f32(w_dw.reshape(16, 9).T), self.const_f32(b_dw), self.const_f32(w_pw.reshape(16, 16)), self.const_f32(b_pw)],
-                 [], [self._tb(out)])
+        self._op(OP_FRONT2, [], [self._tb(out)], out_t=out, w_u8=self.const(wu), w_f32=self.const(wf), b_stem=self.const_f32(b_stem),
+                 s_u8=su, s_f32=sf, act_stem=ACT[act_stem], w_dw=self.const_f32(w_dw.reshape(16, 9).T), b_dw=self.const_f32(b_dw),
+                 w_pw=self.const_f32(w_pw.reshape(16, 16)), b_pw=self.const_f32(b_pw))
         return out
 
     def det_c3_supported(self, cin: int, tail: str) -> bool:
@@ -517,26 +598,24 @@ class ProgramBuilder:
         assert self.det_c3_supported(cin, tail) and ta.C % 8 == 0 and (tb is None or (tb.H, tb.W) == (H, W))
         assert w_cv1.shape[:2] == (32, cin) and w_cv2.shape[:2] == (32, cin) and w_m1.shape[:2] == (32, 32) and w_m2.shape == (32, 32, 3, 3)
         assert w_cv3.shape[:2] == (64, 64)
-        fbits = lambda v: struct.unpack("<i", struct.pack("<f", v))[0]
         wa, sa = self._split_rows(np.concatenate([w_cv1.reshape(32, cin), w_cv2.reshape(32, cin)], 0).astype(np.float64))
         wb, sb = self._split_rows(w_m1.reshape(32, 32).astype(np.float64))
         wc_off, npad, cpad, sc, _ = self.pack_conv_weight(w_m2, force_split=True)
         assert (npad, cpad) == (32, 32)
         wd, sd = self._split_rows(w_cv3.reshape(64, 64).astype(np.float64))
-        f = [src_a, src_b, out, out2, rows_buf, self.const(wa), self.const_f32(np.concatenate([b_cv1, b_cv2])), self.const(wb), self.const_f32(b_m1),
-             wc_off, self.const_f32(b_m2), self.const(wd), self.const_f32(b_cv3)]
-        se = 1.0
+        f = dict(srcA_t=src_a, srcB_t=src_b, out_t=out, out2_t=out2, rows_buf=rows_buf, wA=self.const(wa),
+                 bA=self.const_f32(np.concatenate([b_cv1, b_cv2])), wB=self.const(wb), bB=self.const_f32(b_m1), wC=wc_off, bC=self.const_f32(b_m2),
+                 wD=self.const(wd), bD=self.const_f32(b_cv3))
         if tail == "conv":
             assert w_tail.shape[:2] == (64, 64) and out2 >= 0
             we, se = self._split_rows(w_tail.reshape(64, 64).astype(np.float64))
-            f += [self.const(we), self.const_f32(b_tail), -1]
+            f.update(wE=self.const(we), bE=self.const_f32(b_tail), anchors=-1)
         else:
             assert w_tail.shape[:2] == (48, 64) and rows_buf >= 0
             we, se = self._split_rows(w_tail.reshape(48, 64).astype(np.float64))
-            f += [self.const(we), self.const_f32(b_tail), self.const_f32(np.asarray(anchors, np.float64).reshape(-1))]
-        f += [fbits(sa), fbits(sb), fbits(sc), fbits(sd), fbits(se), fbits(float(det_stride)), cin, {"conv": 1, "detect": 2}[tail],
-              1 if up_a else 0, row0, nrows_total]
-        self._op(OP_DETC3, f, [self._tb(src_a), self._tb(src_b)], [self._tb(out), self._tb(out2), rows_buf])
+            f.update(wE=self.const(we), bE=self.const_f32(b_tail), anchors=self.const_f32(np.asarray(anchors, np.float64).reshape(-1)))
+        self._op(OP_DETC3, [self._tb(src_a), self._tb(src_b)], [self._tb(out), self._tb(out2), rows_buf], sA=sa, sB=sb, sC=sc, sD=sd, sE=se,
+                 det_stride=det_stride, CIN=cin, tail={"conv": 1, "detect": 2}[tail], upA=1 if up_a else 0, row0=row0, nrows_total=nrows_total, **f)
 
     def dsconv_supported(self, cin: int, k: int, stride: int, dil: int, cout: int) -> bool:
         return self.esize == 4 and cin == 16 and k == 3 and stride == 1 and dil == 1 and cout <= 32 and cout % 4 == 0
@@ -552,11 +631,10 @@ class ProgramBuilder:
         wd = w_dw.reshape(cin, 9).T
         wp = np.zeros((coutp, cin)); wp[:cout] = w_pw.reshape(cout, cin)
         bp = np.zeros(coutp); bp[:cout] = b_pw
-        fbits = lambda v: struct.unpack("<i", struct.pack("<f", v))[0]
         zero = self.const_f32(np.zeros(16))
-        self._op(OP_MBCONV, [x, out, res, zero, zero, self.const_f32(wd), self.const_f32(b_dw), self.const_f32(wp),
-                             self.const_f32(bp), 3, 1, 1, 1, ACT[act], 16, 16, coutp, cout, 16, fbits(1.0), fbits(1.0), 2],
-                 [self._tb(x), self._tb(res)], [self._tb(out)])
+        self._op(OP_MBCONV, [self._tb(x), self._tb(res)], [self._tb(out)], in_t=x, out_t=out, res_t=res, w_exp=zero, b_exp=zero,
+                 w_dw=self.const_f32(wd), b_dw=self.const_f32(b_dw), w_pwl=self.const_f32(wp), b_pwl=self.const_f32(bp), K=3, stride=1, pad=1,
+                 dil=1, act=ACT[act], MidPad=16, KS=16, CoutPad=coutp, Cout=cout, Mid16=16, scale_exp=1.0, scale_pwl=1.0, variant=2)
         return out
 
     def expdw_supported(self, H: int, W: int, k: int, stride: int, pad: int, dil: int, cin: int = 0) -> bool:
@@ -584,9 +662,9 @@ class ProgramBuilder:
         be[:mid] = b_exp
         gap = self.buffer(mid, ELEM_F32, "gap") if want_gap else -1
         wd = np.transpose(w_dw.astype(np.float64).reshape(mid, k * k), (1, 0))
-        self._op(OP_EXPDW, [x, out, gap, woff, self.const_f32(be), self.const_f32(wd), self.const_f32(b_dw), k, pad, dil,
-                            ACT[act], cpad, npad, mid, struct.unpack("<i", struct.pack("<f", acc_scale))[0], stride],
-                 [self._tb(x)], [self._tb(out), gap])
+        self._op(OP_EXPDW, [self._tb(x)], [self._tb(out), gap], in_t=x, out_t=out, gap_buf=gap, w_exp=woff, b_exp=self.const_f32(be),
+                 w_dw=self.const_f32(wd), b_dw=self.const_f32(b_dw), K=k, pad=pad, dil=dil, act=ACT[act], Cpad=cpad, Npad=npad, N=mid,
+                 acc_scale=acc_scale, stride=stride)
         return out, gap
 
     # (Cin padded / 32, Cout / 16, k, dilation, has SE) with an mbx_kernel instantiation (csrc/k_mbx.h, engine.cpp PF_OP_MBX)
@@ -637,11 +715,12 @@ class ProgramBuilder:
         assert cin == ti.real_c == ti.C and w_dw.shape == (mid, 1, k, k) and w_pwl.shape[1] == mid
         assert self.mbx_supported(x, k, 1, pad, dil, cout, se_fcs is not None) and waves in (8, 16)
         w1, ct, w2, b2, ks, T, s1, s2 = self._mbx_pack(w_exp, b_exp, w_dw, b_dw, w_pwl, b_pwl)
-        fbits = lambda v: struct.unpack("<i", struct.pack("<f", v))[0]
-        common = [w1, ct, w2, b2, k, pad, dil, ACT[act], ks, T, cout, mid, fbits(s1), fbits(s2)]
+        common = dict(in_t=x, w1=w1, ctile=ct, w2=w2, b2=b2, K=k, pad=pad, dil=dil, act=ACT[act], KS=ks, T=T, Cout=cout, Cexp=mid,
+                      scale1=s1, scale2=s2)
         if se_fcs is None:
             out = self.tensor(ti.H, ti.W, cout, name=out_name)
-            self._op(OP_MBX, [x, out, res, -1, -1] + common + [0, waves], [self._tb(x), self._tb(res)], [self._tb(out)])
+            self._op(OP_MBX, [self._tb(x), self._tb(res)], [self._tb(out)], out_t=out, res_t=res, gap_buf=-1, gate_buf=-1, mode=0, waves=waves,
+                     **common)
             return out
         if se_mode is None:
             se_mode = "store"
@@ -651,15 +730,16 @@ class ProgramBuilder:
         if se_mode == "store":
             assert mid % 32 == 0, "the stored map is written in whole 32-channel tiles"
             dwt = self.tensor(ti.H, ti.W, mid, name=dw_name)
-            self._op(OP_MBX, [x, dwt, -1, gap, -1] + common + [3, 16], [self._tb(x)], [self._tb(dwt), gap])
+            self._op(OP_MBX, [self._tb(x)], [self._tb(dwt), gap], out_t=dwt, res_t=-1, gap_buf=gap, gate_buf=-1, mode=3, waves=16, **common)
             gate = self.fc_pair(gap, w_rd, b_rd, "relu", w_ex, b_ex, "hsigmoid")
             return self.conv(dwt, w_pwl, b_pwl, "none", res=res, gate_buf=gate, out_name=out_name)
         assert mid % 32 == 0, "the recompute pass fetches the face's gates in whole 32-channel tiles (k_mbx.h dma_ct)"
         out = self.tensor(ti.H, ti.W, cout, name=out_name)
-        self._op(OP_MBX, [x, -1, -1, gap, -1] + common + [1, 16], [self._tb(x)], [gap])
+        self._op(OP_MBX, [self._tb(x)], [gap], out_t=-1, res_t=-1, gap_buf=gap, gate_buf=-1, mode=1, waves=16, **common)
         gate = self.fc_pair(gap, w_rd, b_rd, "relu", w_ex, b_ex, "hsigmoid")
         nw2 = waves if (ks, cout // 16, k, dil) in self.MBX_RECOMPUTE_16 else 8
-        self._op(OP_MBX, [x, out, res, -1, gate] + common + [2, nw2], [self._tb(x), self._tb(res), gate], [self._tb(out)])
+        self._op(OP_MBX, [self._tb(x), self._tb(res), gate], [self._tb(out)], out_t=out, res_t=res, gap_buf=-1, gate_buf=gate, mode=2, waves=nw2,
+                 **common)
         return out
 
     CHAIN_SHAPES = ((72, 16), (144, 8))       # (channels, map side) with a basic_chain_kernel instantiation
@@ -677,7 +757,7 @@ class ProgramBuilder:
         assert self.basic_chain_supported(x, len(blocks))
         c = ti.real_c
         out = self.tensor(ti.H, ti.W, c, name=out_name)
-        fields = [x, out, 2 * len(blocks), c]
+        convs = []
         for blk in blocks:
             for wgt, bias in ((blk[0], blk[1]), (blk[2], blk[3])):
                 assert wgt.shape == (c, c, 3, 3)
@@ -685,8 +765,8 @@ class ProgramBuilder:
                 assert npad == _round_up(c, 16) and cpad == _round_up(c, 32)
                 b = np.zeros(npad, np.float64)
                 b[:c] = bias
-                fields += [woff, self.const_f32(b), struct.unpack("<i", struct.pack("<f", acc_scale))[0]]
-        self._op(OP_CHAIN, fields, [self._tb(x)], [self._tb(out)])
+                convs.append(dict(wt=woff, bias=self.const_f32(b), acc_scale=acc_scale))
+        self._op(OP_CHAIN, [self._tb(x)], [self._tb(out)], in_t=x, out_t=out, n_convs=len(convs), C=c, convs=convs)
         return out
 
     BLOCK_SHAPES = ((18, 64), (36, 32), (18, 16))   # (channels, map side) with a basic_block_kernel instantiation
@@ -722,21 +802,21 @@ class ProgramBuilder:
         c = ti.real_c
         out = self.tensor(ti.H, ti.W, ti.C, name=out_name)
         self.tensors[out].real_c = c
-        fields = [x, out, c]
+        convs = []
         for wgt, bias in ((w1, b1), (w2, b2)):
             assert wgt.shape == (c, c, 3, 3)
             woff, npad, acc_scale = self.pack_flatk_weight(wgt)
             b = np.zeros(npad, np.float64)
             b[:c] = bias
-            fields += [woff, self.const_f32(b), struct.unpack("<i", struct.pack("<f", acc_scale))[0]]
-        self._op(OP_BLOCK, fields, [self._tb(x)], [self._tb(out)])
+            convs.append(dict(wt=woff, bias=self.const_f32(b), acc_scale=acc_scale))
+        self._op(OP_BLOCK, [self._tb(x)], [self._tb(out)], in_t=x, out_t=out, C=c, convs=convs)
         return out
 
     def upcat(self, lo: int, skip: int, out_name: str = "") -> int:
         tl, ts = self.tensors[lo], self.tensors[skip]
         assert (ts.H, ts.W) == (2 * tl.H, 2 * tl.W)
         out = self.tensor(ts.H, ts.W, tl.C + ts.C, name=out_name)
-        self._op(OP_UPCAT, [lo, skip, out], [self._tb(lo), self._tb(skip)], [self._tb(out)])
+        self._op(OP_UPCAT, [self._tb(lo), self._tb(skip)], [self._tb(out)], lo_t=lo, skip_t=skip, out_t=out)
         return out
 
     def sepconv_up_can_sum(self, lo: int, skip: int, n_out: int) -> bool:
@@ -793,9 +873,9 @@ class ProgramBuilder:
         if gap_parts:       # per-tile (128 pixels) channel sums of the activated output: the squeeze of the SCSE block behind it, for fc_pair(nparts=...)
             assert self.sepconv_up_can_sum(lo, skip, n) and n == npad
             parts = self.buffer((ts.H * ts.W // 128) * n, ELEM_F32, "sepup.gap_parts")
-        self._op(OP_SEPUP, [lo, skip, out, dwe, self.const_f32(dw_bias), woff, self.const_f32(b), cpad, npad, n, ACT[act],
-                            struct.unpack("<i", struct.pack("<f", acc_scale))[0], dws, skipx, dwl, dwv, parts + 1],
-                 [self._tb(lo), self._tb(skip)], [self._tb(out), skipx, parts])
+        self._op(OP_SEPUP, [self._tb(lo), self._tb(skip)], [self._tb(out), skipx, parts], lo_t=lo, skip_t=skip, out_t=out, dw_e=dwe,
+                 dw_b=self.const_f32(dw_bias), pw_wt=woff, pw_bias=self.const_f32(b), Cpad=cpad, Npad=npad, N=n, act=ACT[act], acc_scale=acc_scale,
+                 dw_skip=dws, skipx_buf=skipx, dw_lo=dwl, dw_v=dwv, gap_parts_plus1=parts + 1)
         return (out, parts) if gap_parts else out
 
     def add_up(self, a: int, b: int, shift: int, act: str, out_name: str = "") -> int:
@@ -804,7 +884,7 @@ class ProgramBuilder:
         assert (tb.H << shift, tb.W << shift, tb.C) == (ta.H, ta.W, ta.C)
         out = self.tensor(ta.H, ta.W, ta.C, name=out_name)
         self.tensors[out].real_c = ta.real_c
-        self._op(OP_ADDUP, [a, b, out, shift, ACT[act]], [self._tb(a), self._tb(b)], [self._tb(out)])
+        self._op(OP_ADDUP, [self._tb(a), self._tb(b)], [self._tb(out)], a_t=a, b_t=b, out_t=out, shift=shift, act=ACT[act])
         return out
 
     def fuse_up_supported(self, y: int, srcs) -> bool:
@@ -828,7 +908,7 @@ class ProgramBuilder:
         assert self.fuse_up_supported(y, [(t, sh) for t, _, _, sh in terms])
         out = self.tensor(ty.H, ty.W, ty.C, name=out_name)
         self.tensors[out].real_c = ty.real_c
-        f = [y, out, ACT[act], len(terms)]
+        src = []
         reads = [self._tb(y)]
         for t, w, b, shift in terms:
             ts = self.tensors[t]
@@ -838,15 +918,15 @@ class ProgramBuilder:
             wt[:, :c] = w.reshape(c, k).T
             bb = np.zeros(ty.C, np.float64)
             bb[:c] = b
-            f += [t, self.const_f32(wt), self.const_f32(bb), shift]
+            src.append(dict(src_t=t, wt=self.const_f32(wt), bias=self.const_f32(bb), shift=shift))
             reads.append(self._tb(t))
-        f += [-1, 0, 0, 0] * (3 - len(terms)) + [ty.real_c]
-        self._op(OP_FUSEUP, f, reads, [self._tb(out)])
+        src += [dict(src_t=-1, wt=0, bias=0, shift=0)] * (3 - len(terms))
+        self._op(OP_FUSEUP, reads, [self._tb(out)], y_t=y, out_t=out, act=ACT[act], nsrc=len(terms), src=src, C=ty.real_c)
         return out
 
     def gap(self, x: int) -> int:
         out = self.buffer(self.tensors[x].C, ELEM_F32, "gap")
-        self._op(OP_GAP, [x, out], [self._tb(x)], [out])
+        self._op(OP_GAP, [self._tb(x)], [out], in_t=x, out_buf=out)
         return out
 
     def fc(self, xbuf: int, weight: np.ndarray, bias: Optional[np.ndarray], act: str,
@@ -859,7 +939,7 @@ class ProgramBuilder:
         boff = self.const_f32(bias) if bias is not None else -1
         s2 = self.const_f32(scale2) if scale2 is not None else -1
         t2 = self.const_f32(shift2) if shift2 is not None else -1
-        self._op(OP_FC, [xbuf, out, woff, boff, k, n, ACT[act], s2, t2, ACT[act2]], [xbuf], [out])
+        self._op(OP_FC, [xbuf], [out], x_buf=xbuf, y_buf=out, wt=woff, bias=boff, K=k, N=n, act=ACT[act], scale2=s2, shift2=t2, act2=ACT[act2])
         return out
 
     def fc_pair_fuses(self, k: int, r: int, n: int) -> bool:
@@ -885,10 +965,9 @@ class ProgramBuilder:
             return self.fc(hid, w2, b2, act2)
         out = self.buffer(n, ELEM_F32, "fc2")
         cf = lambda v: self.const_f32(v) if v is not None else -1
-        self._op(OP_FC2, [xbuf, out, self.const_f32(np.transpose(w1.astype(np.float64), (1, 0))), cf(b1), k, r, ACT[act1],
-                          cf(scale2), cf(shift2), ACT[act1b], self.const_f32(np.transpose(w2.astype(np.float64), (1, 0))), cf(b2), n, ACT[act2],
-                          nparts, struct.unpack("<i", struct.pack("<f", float(xscale)))[0]],
-                 [xbuf], [out])
+        self._op(OP_FC2, [xbuf], [out], x_buf=xbuf, y_buf=out, w1=self.const_f32(np.transpose(w1.astype(np.float64), (1, 0))), b1=cf(b1), K=k, R=r,
+                 act1=ACT[act1], scale2=cf(scale2), shift2=cf(shift2), act1b=ACT[act1b],
+                 w2=self.const_f32(np.transpose(w2.astype(np.float64), (1, 0))), b2=cf(b2), N=n, act2=ACT[act2], nparts=nparts, xscale=xscale)
         return out
 
     def scse_can_sum(self, x: int) -> bool:
@@ -902,14 +981,12 @@ class ProgramBuilder:
         ti = self.tensors[x]
         out = self.tensor(ti.H, ti.W, ti.C, name=out_name)
         woff = self.const_f32(sse_w.reshape(-1))
-        bbits = struct.unpack("<i", struct.pack("<f", float(sse_b)))[0]
-        fields = [x, out, cse_buf, woff, bbits]
         parts = -1
         if gap_parts:
             assert self.scse_can_sum(x)
             parts = self.buffer((ti.H * ti.W // SCSE_TILE) * ti.C, ELEM_F32, "scse.gap_parts")
-            fields.append(parts + 1)
-        self._op(OP_SCSE, fields, [self._tb(x), cse_buf], [self._tb(out), parts])
+        self._op(OP_SCSE, [self._tb(x), cse_buf], [self._tb(out), parts], in_t=x, out_t=out, cse_buf=cse_buf, sse_w=woff, sse_b=sse_b,
+                 gap_parts_plus1=parts + 1)
         return (out, parts) if gap_parts else out
 
     def face_attrs(self, sources, weight: np.ndarray, bias: np.ndarray) -> int:
@@ -919,11 +996,11 @@ class ProgramBuilder:
         assert len(sources) == 3 and sum(c for _, _, c, _, _ in sources) == 640
         assert weight.shape == (7, 640) and bias.shape == (7,)
         out = self.buffer(FACE_ATTR_REC, ELEM_F32, "face_attrs", pinned=True)
-        f = [out, self.const_f32(weight.reshape(7, 640)), self.const_f32(bias)]
+        wt, boff = self.const_f32(weight.reshape(7, 640)), self.const_f32(bias)
         for buf, nparts, c, ld, scale in sources:
             assert self.bufs[buf].elems == nparts * ld and c <= ld
-            f += [buf, nparts, c, ld, struct.unpack("<i", struct.pack("<f", float(scale)))[0]]
-        self._op(OP_FACEATTR, f, [b for b, *_ in sources], [out])
+        self._op(OP_FACEATTR, [b for b, *_ in sources], [out], out_buf=out, wt=wt, bias=boff,
+                 src=[dict(src_buf=buf, nparts=nparts, C=c, ld=ld, scale=scale) for buf, nparts, c, ld, scale in sources])
         return out
 
     def hmdec(self, val_buf: int, idx_buf: int, feat: int, off_w: np.ndarray, off_b: np.ndarray, points: int,
@@ -932,8 +1009,8 @@ class ProgramBuilder:
         score = self.buffer(points, ELEM_F32, "score", pinned=True)
         woff = self.const_f32(off_w)
         boff = self.const_f32(off_b)
-        self._op(OP_HMDEC, [val_buf, idx_buf, feat, woff, boff, points, nslots, loc, score],
-                 [val_buf, idx_buf, self._tb(feat)], [loc, score])
+        self._op(OP_HMDEC, [val_buf, idx_buf, self._tb(feat)], [loc, score], val_buf=val_buf, idx_buf=idx_buf, feat_t=feat, off_wt=woff,
+                 off_bias=boff, P=points, nslots=nslots, loc_buf=loc, score_buf=score)
         return loc, score
 
     def maxpool(self, x: int, out: Optional[int] = None, out_name: str = "") -> int:
@@ -941,16 +1018,15 @@ class ProgramBuilder:
         oh, ow = (ti.H + 1) // 2, (ti.W + 1) // 2
         if out is None:
             out = self.tensor(oh, ow, ti.C, name=out_name)
-        self._op(OP_MAXPOOL, [x, out], [self._tb(x)], [self._tb(out)])
+        self._op(OP_MAXPOOL, [self._tb(x)], [self._tb(out)], in_t=x, out_t=out)
         return out
 
     def copy(self, x: int, out: int, out_cs: int = 1, up: int = 1):
-        self._op(OP_COPY, [x, out, out_cs, up], [self._tb(x)], [self._tb(out)])
+        self._op(OP_COPY, [self._tb(x)], [self._tb(out)], in_t=x, out_t=out, out_cs=out_cs, up=up)
 
     def detdec(self, x: int, rows_buf: int, row0: int, stride: float, anchors: np.ndarray, nrows_total: int):
         aoff = self.const_f32(np.asarray(anchors, np.float64).reshape(-1))
-        sbits = struct.unpack("<i", struct.pack("<f", float(stride)))[0]
-        self._op(OP_DETDEC, [x, rows_buf, row0, sbits, aoff, nrows_total], [self._tb(x)], [rows_buf])
+        self._op(OP_DETDEC, [self._tb(x)], [rows_buf], in_t=x, rows_buf=rows_buf, row0=row0, stride=stride, anchors=aoff, nrows_total=nrows_total)
 
     # ---- assembly ---------------------------------------------------------------------------
     def _item_units(self, b: _Buf) -> int:

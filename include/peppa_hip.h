@@ -322,6 +322,11 @@ int pf_set_option(pf_handle* h, int option, int value);
  * when profiling is enabled.  names: '\n'-separated kernel tags; ms: same order. */
 int pf_profile_enable(pf_handle* h, int on);
 int pf_profile_fetch(pf_handle* h, char* names, size_t names_cap, float* ms, int* counts, int cap, int* n_out);
+/* Kernels launched by the engine since profiling was enabled (nothing is recorded while it is off), in launch order: '\n'-separated
+ * names as the launch sites spell them, template arguments included, e.g. "(conv3x3_halo_split_kernel<48, 8, 1, 256>)".  For tests
+ * of the dispatch.  At most names_cap - 1 bytes are written; *bytes_needed is the size that holds everything, *n_out the number
+ * of launches (the log keeps the first 65536).  pf_profile_enable clears it. */
+int pf_launch_log(pf_handle* h, char* names, size_t names_cap, int* n_out, size_t* bytes_needed);
 
 #ifdef __cplusplus
 }

@@ -85,6 +85,7 @@ def _declare(lib):
     lib.pf_set_option.argtypes = [vp, i, i]
     lib.pf_profile_enable.argtypes = [vp, i]
     lib.pf_profile_fetch.argtypes = [vp, C.c_char_p, sz, fp, ip, i, ip]
+    lib.pf_launch_log.argtypes = [vp, C.c_char_p, sz, ip, C.POINTER(sz)]
     lib.pf_host_alloc.argtypes = [sz, C.POINTER(vp)]
     lib.pf_host_free.argtypes = [vp]
     lib.pf_host_alloc.restype = i
@@ -113,7 +114,7 @@ def _declare(lib):
         getattr(lib, name).restype = i
     for name in ("pf_create", "pf_sync", "pf_load_program", "pf_landmark_forward", "pf_detector_forward",
                  "pf_read_tensor", "pf_detect", "pf_landmarks", "pf_run_frames", "pf_run_frames_planted",
-                 "pf_profile_enable", "pf_profile_fetch", "pf_letterbox", "pf_nms_rows", "pf_crop_faces", "pf_set_frame", "pf_forget_frames", "pf_set_option"):
+                 "pf_profile_enable", "pf_profile_fetch", "pf_launch_log", "pf_letterbox", "pf_nms_rows", "pf_crop_faces", "pf_set_frame", "pf_forget_frames", "pf_set_option"):
         getattr(lib, name).restype = i
     return lib
 
@@ -655,6 +656,14 @@ class Engine:
         self._check(self.lib.pf_profile_fetch(self.h, names, 16384, ms, cnt, cap, C.byref(n)), "pf_profile_fetch")
         tags = [t for t in names.value.decode().split("\n") if t]
         return {tags[k]: (float(ms[k]), int(cnt[k])) for k in range(n.value)}
+
+    def launch_log(self):
+        """Kernels launched since ``profile_enable(True)``, in order, as the launch sites spell them (template arguments included)."""
+        n, need = C.c_int(0), C.c_size_t(0)
+        self._check(self.lib.pf_launch_log(self.h, None, 0, C.byref(n), C.byref(need)), "pf_launch_log")
+        names = C.create_string_buffer(need.value)
+        self._check(self.lib.pf_launch_log(self.h, names, need.value, C.byref(n), C.byref(need)), "pf_launch_log")
+        return [t for t in names.value.decode().split("\n") if t]
 
 
 class BatchEngine:

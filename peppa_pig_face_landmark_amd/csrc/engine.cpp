@@ -127,6 +127,7 @@ struct pf_handle {
     bool profiling = false;
     std::map<std::string, ProfEntry> prof;
     std::vector<std::string> prof_order;
+    std::vector<const char*> launch_log;      // spelled-out kernel of every PF_LAUNCH made while profiling is on (pf_launch_log)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
@@ -144,11 +145,17 @@ namespace { void comm_release(pf_handle* h); }   // comm.inl
         return 1;                                         \
     } while (0)
 
+// Launch log (pf_launch_log): while profiling is on, every PF_LAUNCH leaves the kernel as it is spelled at the launch site, template
+// arguments included ("(conv3x3_halo_split_kernel<48, 8, 1, 256>)"), so that a test of the dispatch knows which instance ran.
+// Off otherwise: one predictable branch per launch.  mbx_launch.cpp (its own translation unit) is not logged.
+constexpr size_t PF_LAUNCH_LOG_CAP = 1 << 16;
+
 // every kernel launch is checked where it is made: a bad launch configuration (too much LDS, too many
 // registers for the block size) must not surface one call later.  `h` is in scope at every launch site.
 #undef PF_LAUNCH
 #define PF_LAUNCH(kernel, grid, block, stream, ...)                                                          \
     do {                                                                                                     \
+        if (h->profiling && h->launch_log.size() < PF_LAUNCH_LOG_CAP) h->launch_log.push_back(#kernel);      \
         hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__);                                     \
         const hipError_t _le = hipGetLastError();                                                            \
         if (_le != hipSuccess) PF_FAIL(h, "launch of %s failed: %s (%s:%d)", #kernel, hipGetErrorString(_le), __FILE__, __LINE__); \
@@ -659,6 +666,24 @@ int pf_profile_enable(pf_handle* h, int on) {
     h->profiling = on != 0;
     h->prof.clear();
     h->prof_order.clear();
+    h->launch_log.clear();
+    return 0;
+}
+
+int pf_launch_log(pf_handle* h, char* names, size_t names_cap, int* n_out, size_t* bytes_needed) {
+    if (!h) return 1;
+    std::string joined;
+    for (const char* k : h->launch_log) {
+        joined += k;
+        joined += '\n';
+    }
+    if (names && names_cap) {
+        const size_t c = std::min(names_cap - 1, joined.size());
+        memcpy(names, joined.data(), c);
+        names[c] = 0;
+    }
+    if (n_out) *n_out = (int)h->launch_log.size();
+    if (bytes_needed) *bytes_needed = joined.size() + 1;
     return 0;
 }
 

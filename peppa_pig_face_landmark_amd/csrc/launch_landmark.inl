@@ -205,6 +205,8 @@ static int launch_sepup(pf_handle* h, const Program& p, const PfSepupOp& o, int 
         s.dw_v = (const float*)p.cptr(o.dw_v);
         s.gap_part = o.gap_parts_plus1 > 0 ? (float*)p.buf_ptr(o.gap_parts_plus1 - 1) : nullptr;
         if (s.gap_part && !(a.Npad == 256)) PF_FAIL(h, "sepup: per-tile channel sums need the 256-output instance");
+        // one K step per tile leaves nothing between a fast wave's next tile sums and a slow wave's read of the previous ones (k_sepup.h gsum)
+        if (s.gap_part && a.Cpad < 64) PF_FAIL(h, "sepup: per-tile channel sums need at least two K steps (Cpad %d < 64)", a.Cpad);
         s.wt = (const unsigned char*)a.wt; s.bias = a.bias; s.skipx = (unsigned char*)p.buf_ptr(o.skipx_buf);
         s.B = B; s.H = to.H; s.C1 = tl.C; s.C2 = tk.C; s.loLd = tl.ld; s.skipLd = tk.ld; s.outLd = to.ld;
         s.N = a.N; s.Cpad = a.Cpad; s.act = a.act; s.acc_scale = a.acc_scale; s.dbg = h->dbg; s.range_slot = a.range_slot;

@@ -821,10 +821,11 @@ class ProgramBuilder:
 
     def sepconv_up_can_sum(self, lo: int, skip: int, n_out: int) -> bool:
         """Will ``sepconv_up`` run as the pipelined kernel's 256-output instance (csrc/k_sepup.h, engine.cpp pipe_ok), whose consumers can
-        leave per-tile channel sums of the output behind (``gap_parts=True``)?"""
+        leave per-tile channel sums of the output behind (``gap_parts=True``)?  At least two K steps (Cpad >= 64): with one, a fast wave
+        of the kernel could overwrite the tile's sums in LDS before a slow wave has read the previous tile's."""
         tl, ts = self.tensors[lo], self.tensors[skip]
         return (self.split and n_out == 256 and ts.W in (16, 32, 64) and (ts.H * ts.W) % 128 == 0 and (ts.H * ts.W) // 128 >= 2
-                and tl.C % 32 == 0 and ts.C % 8 == 0 and ts.C <= 64 and _round_up(tl.C + ts.C, 32) <= 640)
+                and tl.C % 32 == 0 and ts.C % 8 == 0 and ts.C <= 64 and 64 <= _round_up(tl.C + ts.C, 32) <= 640)
 
     def sepconv_up(self, lo: int, skip: int, dw_weight: np.ndarray, dw_bias: np.ndarray, pw_weight: np.ndarray,
                    pw_bias: np.ndarray, act: str, out_name: str = "", gap_parts: bool = False):

@@ -18,7 +18,8 @@ def _declared_symbols():
 def test_header_declares_the_boundary():
     syms = _declared_symbols()
     for must in ("pf_create", "pf_destroy", "pf_load_program", "pf_landmark_forward", "pf_detector_forward",
-                 "pf_detect", "pf_landmarks", "pf_run_frames", "pf_last_error"):
+                 "pf_detect", "pf_landmarks", "pf_run_frames", "pf_last_error", "pf_read_tensor", "pf_profile_enable", "pf_profile_fetch",
+                 "pf_launch_log"):
         assert must in syms
 
 

@@ -15,6 +15,10 @@
 #include <vector>
 
 #include "k_conv_gemm.h"
+#include "k_conv_split.h"
+#include "k_expdw.h"
+#include "k_halo.h"
+#include "k_sepup_patch.h"
 #include "k_layers.h"
 #include "k_mbconv.h"
 #include "k_chain.h"

@@ -1,7 +1,4 @@
-// The stem conv of the landmark networks on the matrix cores (round 4).  (Round 4's lm_front_kernel -- conv_stem + blocks.0.0 + blocks.1.0
-// in one launch, 13 barrier-separated phases on a 64-pixel tile -- lived here too: correct, 0.76 against 0.51 ms for the three launches
-// it replaced, never on by default; removed in round 6, when the shallow two-barrier fusion of conv_stem + blocks.0.0 (k_front2.h) took
-// its place.  Its measurements stay in DESIGN.md section 9, round 4.)
+// The stem conv of the landmark networks on the matrix cores (round 4).  The fusion of conv_stem + blocks.0.0 is k_front2.h.
 #pragma once
 #include "pf_common.h"
 #include "k_det.h"
@@ -9,8 +6,8 @@
 // ---- the stem conv alone on the matrix cores (round 4) ---------------------------------------------------------------------------------
 // conv_stem of the Student (3 -> 16, hard-swish) and of the Teacher's HRNet (3 -> 64, relu): 3x3 stride 2 on the uint8 crop.  The VALU
 // kernel (k_layers.h stem_conv_kernel: 27 byte loads and 27 x 16 FMAs per output pixel and 16-channel group) ran at 113 us (Student) /
-// 700 us (Teacher) per 256 crops against 54 / 215 us for writing its output.  Same staging and K order as lm_front_kernel above, but a
-// SHALLOW kernel: one barrier, small LDS footprint, many workgroups per CU -- the shape that works on this chip.
+// 700 us (Teacher) per 256 crops against 54 / 215 us for writing its output.  A SHALLOW kernel (weight
+// fragments by k_det.h's det_wfrag): one barrier, small LDS footprint, many workgroups per CU -- the shape that works on this chip.
 struct StemMfmaArgs {
     const void* in;           // u8 [B][H][W][3] (1/255 folded into w_u8) or f32 [B][3][H][W]
     float* out;               // [B][OH][OW][outLd], 16 * NT channels

@@ -1,5 +1,5 @@
 // The Student's hero conv (up2.conv2: 3x3, 128 -> 128 channels on 64 x 64 maps, f32s; DecoderBlock.conv2, model.py:165-172) with the
-// weight stream TWO steps ahead (round 4).  Same tiling and arithmetic as conv3x3_halo_split_kernel<128, 4, 2> (k_conv_gemm.h): a
+// weight stream TWO steps ahead (round 4).  Same tiling and arithmetic as conv3x3_halo_split_kernel<128, 4, 2> (k_halo.h): a
 // workgroup of 8 waves owns two image rows (128 pixels) x 128 output channels, the (2 + 2) x 64 input pixels of a 32-channel chunk
 // sit in LDS as split hi / lo planes, the nine taps are shifted fragment reads, weights stream per (chunk, tap) by LDS-DMA.  There
 // the stream had ONE step of look-ahead and every step ended in __syncthreads() (which drains vmcnt): round 3's ablations priced the

@@ -7,7 +7,7 @@
 // on its own with no workgroup barrier (a workgroup is four independent waves; wave-level LDS ordering
 // only), in sub-chunks of 16 expanded channels:
 //   * the patch's input halo is held in REGISTERS as split-precision MFMA pixel fragments (hi/lo f16,
-//     k_conv_gemm.h), loaded and split once;
+//     k_conv_split.h), loaded and split once;
 //   * expand: 3 x v_mfma_f32_16x16x32_f16 per 32 input channels and 16x16 tile -> +bias, act, zero
 //     outside the image (the depthwise conv zero-pads the EXPANDED map) -> E[halo][16] f32 in LDS;
 //   * depthwise 3x3 (+bias, act) in f32 from LDS -> D[patch][32] f32 in LDS;

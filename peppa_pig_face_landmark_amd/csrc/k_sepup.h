@@ -1,7 +1,7 @@
 // Fused DecoderBlock front end (model.py:184-189 + SeparableConv2d :15-43), round-3 kernel: bilinear x2 upsample of the
 // low-res map + concat with the skip connection + depthwise 3x3 (+BN) as the PRODUCER of a split-precision pointwise
 // GEMM (3 x v_mfma_f32_16x16x32_f16 per product, f32 accumulate) -- the operator of sepup_patch_kernel
-// (k_conv_gemm.h), restructured around what that kernel's profile showed (profiles/r02_run2_hero_timing_ablations.md):
+// (k_sepup_patch.h), restructured around what that kernel's profile showed (profiles/r02_run2_hero_timing_ablations.md):
 // 0.36 of its 0.65 ms was "skeleton", a serial chain per 128-pixel workgroup of prologue, nine two-barrier K steps that
 // each waited for an LDS-DMA issued inside the same step, a skip-connection step made of dependent global loads, and an
 // epilogue -- overlapped only by the one other workgroup resident on the CU; no unit was above 45 % busy.
@@ -133,16 +133,16 @@ __global__ __launch_bounds__(512) void sepup_skip_kernel(SepupArgs a) {
 // position class of a row / column: 0 first, 1 last, 2 even, 3 odd (ir.py::sepconv_up builds the filters in this order)
 __device__ __forceinline__ int pf_pos_class(int v, int n) { return v == 0 ? 0 : (v == n - 1 ? 1 : 2 + (v & 1)); }
 
-// P_BY_CONS: the consumer waves issue the patch / filter requests too (the producers' step is the longer one at BN = 128: 774 cycles
-// of request issue + 1 600 of work against 388 + 765 + 754, profiles/r05_run51_sepup_roles.txt).  BIAS_REG: the pointwise bias lives in
-// the consumers' registers instead of LDS -- the 512 bytes that keep a fourth ring stage (D = 4) from fitting beside BN = 128.
+// The producers issue the patch / filter requests; W_BY_PROD: they issue the pointwise weights' requests too (BN = 256, where the
+// consumers are twice as loaded), otherwise the consumers do (BN = 128).  Patch requests from the consumer waves and the pointwise bias in
+// registers for a fourth ring stage were measured and not kept (profiles/r05_run51_sepup_roles.txt).
 // VCOL (round 6): the producers' step is bound by its own VALU instruction stream (with requests, patch reads, MFMAs and stores all
 // compiled out the launch still takes 64 % of its time: profiles/r06_run5_ub_sepup_ablate.txt), 92 packed operations per thread of which
 // 32 only interpolate vertically.  The vertical bilinear weights and the depthwise filter's zero padding above / below the image are
 // linear in the filter, so they fold into it at pack time: out[dy][dx] = sum_j sum_kx V[row class of dy][j][kx] * hrow[j][dx + kx] on the
 // horizontally interpolated patch rows -- 36 fma as before, no `u` window (60 packed operations), twice the filter words per chunk
 // (one 3 x 3 set per image row of the tile, chosen by the row's class when the tile's requests are set up).
-template <int BN, int W, int D, bool W_BY_PROD, bool DEFER, bool P_BY_CONS = false, bool BIAS_REG = false, bool VCOL = false>
+template <int BN, int W, int D, bool W_BY_PROD, bool DEFER, bool VCOL = false>
 __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
     constexpr int TR = 128 / W;                          // image rows per tile
     constexpr int PC = W / 2 + 2;                        // patch columns (one replicated column each side)
@@ -158,20 +158,19 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
     constexpr int WI = BN * 8 / 512;                     // weight DMA wave-instructions per wave (of the issuing role) and stage
     constexpr int WN = BN / 2, NT = WN / 16;             // consumers: 4 (pixels) x 2 (channels) waves, 32 x WN per wave
     constexpr int NV = NT * 2;                           // output vectors (4 channels of one pixel) per consumer lane and tile
-    constexpr int EXP_P = (P_BY_CONS ? 0 : PI) + (W_BY_PROD ? WI : 0);      // requests per iteration of a producer / consumer wave in steady state
-    constexpr int EXP_C = (P_BY_CONS ? PI : 0) + (W_BY_PROD ? 0 : WI);
-    constexpr int BIAS_BYTES = BIAS_REG ? 0 : BN * 4;
+    constexpr int EXP_P = PI + (W_BY_PROD ? WI : 0);     // requests per iteration of a producer / consumer wave in steady state
+    constexpr int EXP_C = W_BY_PROD ? 0 : WI;
     constexpr bool GAP_OK = !DEFER && W_BY_PROD;         // channel sums of the output (a.gap_part): the instance whose consumers count no vmcnt
     constexpr int GAP_BYTES = GAP_OK ? 4 * BN * 4 : 0;   // [pixel quarter wm][channel]
     static_assert(PATCH_SLOTS + FILT_SLOTS <= P_INSTR * 64 && 1024 <= P_INSTR * 64, "patch/filter stage");
     static_assert(D >= 2 && (D - 2) * (PI + WI) + 1 < 63, "ring depth");
-    static_assert(2 * X_BYTES + D * W_BYTES + D * P_BYTES + BIAS_BYTES + GAP_BYTES <= 160 * 1024, "LDS budget");
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * X_BYTES + D * W_BYTES + D * P_BYTES + BIAS_BYTES + GAP_BYTES];
+    static_assert(2 * X_BYTES + D * W_BYTES + D * P_BYTES + BN * 4 + GAP_BYTES <= 160 * 1024, "LDS budget");
+    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * X_BYTES + D * W_BYTES + D * P_BYTES + BN * 4 + GAP_BYTES];
     unsigned char* const xbase = smem;
     unsigned char* const wbase = smem + 2 * X_BYTES;
     unsigned char* const pbase = wbase + D * W_BYTES;
     float* const sbias = reinterpret_cast<float*>(pbase + D * P_BYTES);
-    float* const gsum = reinterpret_cast<float*>(pbase + D * P_BYTES + BIAS_BYTES);
+    float* const gsum = reinterpret_cast<float*>(pbase + D * P_BYTES + BN * 4);
 
     const int t = threadIdx.x;
     const int lane = t & 63;
@@ -194,7 +193,7 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
     const size_t wrow_bytes = (size_t)NK * 128;
     const bool prof = (pf_dbg(a) & 64) != 0;
 
-    if constexpr (!BIAS_REG) { for (int i = t; i < BN; i += 1024) sbias[i] = a.bias[i]; }
+    for (int i = t; i < BN; i += 1024) sbias[i] = a.bias[i];
 
     // tile j of this workgroup -> (face, first row, global tile id)
     auto tile_of = [&](int j, int& face, int& y0, int& gt) {
@@ -204,7 +203,7 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
         y0 = s * TR;
         gt = face * TPF + s;
     };
-    // ---- the two request streams (LDS-DMA from inline asm; either role can issue them with its role-local thread index) -------
+    // ---- the two request streams (LDS-DMA from inline asm; the weights by either role, with its role-local thread index) -------
     // patch + position-class filters (or the ready-made skip-chunk operand) of step (dj, dcb) -> P ring stage
     const float* dsrc[PI];                                          // per-lane source of this wave's requests, current DMA tile
     int dadv[PI];                                                   // floats the source advances per channel chunk (0 for padding slots)
@@ -281,14 +280,13 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
             for (int dx = 0; dx < 2; ++dx)
                 xoff[dy][dx] = pf_lds_chunk_off((2 * brow + dy) * W + 2 * bn + dx, cp >> 2) + (cp & 3) * 4;
         const float ml = bn == 0 ? 0.f : 1.f, mr = bn == BCOLS - 1 ? 0.f : 1.f;     // upsampled columns -1 / W are padding
-        if constexpr (!P_BY_CONS) dma_tile(0);
+        dma_tile(0);
 #pragma unroll
         for (int k = 0; k < D - 1; ++k) {
-            if (!P_BY_CONS && issued_p < S) { dma_issue(issued_p % D); ++issued_p; }
+            if (issued_p < S) { dma_issue(issued_p % D); ++issued_p; }
             if (W_BY_PROD && issued_w < S) { w_issue(issued_w); ++issued_w; }
         }
-        if (EXP_P > 0) pf_wait_vm_barrier<(D - 2) * EXP_P>();       // stage 0 has landed (S >= NK >= D - 1 always holds)
-        else pf_wait_vm_barrier<63>();                              // no requests of its own: nothing but the rendezvous
+        pf_wait_vm_barrier<(D - 2) * EXP_P>();                      // stage 0 has landed (S >= NK >= D - 1 always holds)
 
         int pj = 0, pcb = 0;                                        // produce position
         float mt = 1.f, mb = 1.f;                                    // upsampled rows -1 / H are padding
@@ -306,7 +304,7 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
             const unsigned long long c0 = prof ? pf_clock() : 0;
             // requests of this iteration: the stage read D - 1 steps from now and (W_BY_PROD) the weights consumed D - 1 iterations from now
             int nreq = 0;
-            if (!P_BY_CONS && issued_p < S && !(pf_dbg(a) & 2)) { dma_issue(issued_p % D); ++issued_p; nreq += PI; }
+            if (issued_p < S && !(pf_dbg(a) & 2)) { dma_issue(issued_p % D); ++issued_p; nreq += PI; }
             if (W_BY_PROD && g >= 1 && issued_w < S && !(pf_dbg(a) & 1)) { w_issue(issued_w); ++issued_w; nreq += WI; }
             const unsigned long long c1 = prof ? pf_clock() : 0;
             if (g < S) {
@@ -400,8 +398,7 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
             }
             const unsigned long long c2 = prof ? pf_clock() : 0;
             // end of step g: what was requested D - 2 iterations ago and earlier must have landed
-            if (EXP_P == 0) pf_wait_vm_barrier<63>();
-            else if (nreq == EXP_P) pf_wait_vm_barrier<(D - 2) * EXP_P>();
+            if (nreq == EXP_P) pf_wait_vm_barrier<(D - 2) * EXP_P>();
             else pf_wait_vm_barrier<0>();
             if (prof) { t_dma += c1 - c0; t_work += c2 - c1; t_wait += pf_clock() - c2; }
         }
@@ -421,17 +418,8 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
         // while the producers' VALU work fills the slots in between -- the other way round the producers starve them of issue slots
         // (0.548 -> 0.528 ms per 256 faces at 64 x 64; producers first: 0.56; profiles/r05_run27_wave_priority_ab3.txt)
         pf_setprio<3>();
-        pf_f32x4 breg[BIAS_REG ? NT : 1];                           // BIAS_REG: this lane's NT x 4 bias values, fetched before any request is in flight
-        if constexpr (BIAS_REG) {
-#pragma unroll
-            for (int j = 0; j < NT; ++j) breg[j] = *reinterpret_cast<const pf_f32x4*>(a.bias + wn * WN + j * 16 + crow);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) asm volatile("" : "+v"(breg[j]));        // (landed: the compiler waits for them here, not inside the ring)
-        }
-        if constexpr (P_BY_CONS) dma_tile(0);
 #pragma unroll
         for (int k = 0; k < D - 1; ++k) {
-            if (P_BY_CONS && issued_p < S) { dma_issue(issued_p % D); ++issued_p; }
             if (!W_BY_PROD && issued_w < S) { w_issue(issued_w); ++issued_w; }
         }
         if (EXP_C > 0) pf_wait_vm_barrier<(D - 2) * EXP_C>();
@@ -467,7 +455,6 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
                     gap_gt = -1;
                 }
             }
-            if (P_BY_CONS && issued_p < S && !(pf_dbg(a) & 2)) { dma_issue(issued_p % D); ++issued_p; nreq += PI; }
             if (g >= 1) {
                 const int c = g - 1;
                 if (!W_BY_PROD && issued_w < S && !(pf_dbg(a) & 1)) { w_issue(issued_w); ++issued_w; nreq += WI; }
@@ -514,7 +501,7 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
                     const bool want_gap = GAP_OK && a.gap_part != nullptr;
 #pragma unroll
                     for (int j = 0; j < NT; ++j) {
-                        const pf_f32x4 bv = BIAS_REG ? breg[BIAS_REG ? j : 0] : *reinterpret_cast<const pf_f32x4*>(sbias + wn * WN + j * 16 + crow);
+                        const pf_f32x4 bv = *reinterpret_cast<const pf_f32x4*>(sbias + wn * WN + j * 16 + crow);
                         pf_f32x4 gs = pf_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                         for (int i = 0; i < 2; ++i) {
@@ -568,4 +555,3 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
         if (prof && lane == 0) { atomicAdd(a.prof + 4, t_dma); atomicAdd(a.prof + 5, t_mma); atomicAdd(a.prof + 6, t_epi); atomicAdd(a.prof + 7, t_wait); atomicAdd(a.prof + 8, 1ull); }
     }
 }
-

@@ -1,5 +1,5 @@
-// Launchers of the landmark networks' encoder / decoder ops: dense conv (k_conv_gemm.h, k_hero.h, k_pwhead.h), the fused decoder front end
-// (k_sepup.h), the inverted-residual blocks (k_mbconv.h, k_mbx.h, expand + depthwise) and the Student's fused front (k_front2.h).
+// Launchers of the landmark networks' encoder / decoder ops: dense conv (k_conv_gemm.h, k_conv_split.h, k_halo.h, k_hero.h, k_pwhead.h), the fused decoder front end
+// (k_sepup.h, k_sepup_patch.h), the inverted-residual blocks (k_mbconv.h, k_mbx.h, k_expdw.h) and the Student's fused front (k_front2.h).
 // Included by engine.cpp only.
 template <typename T, bool SPLIT>
 static int launch_conv(pf_handle* h, const Program& p, const PfConvOp& o, int B, unsigned* range_slot) {
@@ -33,13 +33,12 @@ static int launch_conv(pf_handle* h, const Program& p, const PfConvOp& o, int B,
     int cfg = o.cfg;
     if (cfg < 0) {
         const int t16 = a.Npad / 16;
-        int best_q = 0, best_nt = 0, best_cost = 1 << 30;
+        int best_nt = 0, best_cost = 1 << 30;
         for (int q = (t16 + 7) / 8; q <= (t16 + 7) / 8 + 3; ++q) {
             const int nt = (t16 + q - 1) / q;
             if (nt < 1 || nt > 8) continue;
-            if (q * nt < best_cost) { best_cost = q * nt; best_q = q; best_nt = nt; }
+            if (q * nt < best_cost) { best_cost = q * nt; best_nt = nt; }
         }
-        (void)best_q;
         cfg = cfg_of_nt[best_nt];
         // 160 output channels (stage-5 projections, K = 672 / 960): one 128 x 160 tile reads the wide input once
         // instead of twice (two 80-channel tiles); split-precision pointwise only
@@ -132,7 +131,7 @@ static int launch_conv(pf_handle* h, const Program& p, const PfConvOp& o, int B,
             return 0;
         }
     }
-    // plain pointwise convs whose K depth has an unrolled instance (two K steps of look-ahead, k_conv_gemm.h): the Student's
+    // plain pointwise convs whose K depth has an unrolled instance (two K steps of look-ahead, k_conv_split.h): the Student's
     // stage-3 to stage-5 projections at 256 x 256 and a few neighbours; every other depth takes the rolled loop of the same kernel
     if constexpr (SPLIT) {
         if (use_split && pointwise && !a.amax_val) {
@@ -223,8 +222,8 @@ static int launch_sepup(pf_handle* h, const Program& p, const PfSepupOp& o, int 
     if (to.W == WW) {                                                                                              \
         if (nskip > 0 && tk.C <= 32) PF_LAUNCH((sepup_skip_kernel<WW, 32>), sg, dim3(512), h->stream, s);          \
         else if (nskip > 0) PF_LAUNCH((sepup_skip_kernel<WW, 64>), sg, dim3(512), h->stream, s);                   \
-        if (a.Npad == 128) PF_LAUNCH((sepup_pipe_kernel<128, WW, 3, false, true, false, false, (WW >= 32)>), dim3(wgs), dim3(1024), h->stream, s);     \
-        else PF_LAUNCH((sepup_pipe_kernel<256, WW, 2, true, false, false, false, (WW >= 32)>), dim3(wgs), dim3(1024), h->stream, s);                   \
+        if (a.Npad == 128) PF_LAUNCH((sepup_pipe_kernel<128, WW, 3, false, true, (WW >= 32)>), dim3(wgs), dim3(1024), h->stream, s);                   \
+        else PF_LAUNCH((sepup_pipe_kernel<256, WW, 2, true, false, (WW >= 32)>), dim3(wgs), dim3(1024), h->stream, s);                   \
     }
         PF_SEPUP_CASE(64) PF_SEPUP_CASE(32) PF_SEPUP_CASE(16)
 #undef PF_SEPUP_CASE

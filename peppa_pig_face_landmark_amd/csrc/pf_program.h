@@ -66,7 +66,7 @@ enum PfOpCode : int32_t {
     PF_OP_DETUNIT = 18,
     PF_OP_DETC3 = 19,
     PF_OP_DETSTEM = 20,
-    // 21: PF_OP_LMFRONT (round 4: conv_stem + blocks.0.0 + blocks.1.0 in one launch) -- removed in round 6, see PF_OP_FRONT2
+    // (21 is unassigned)
     PF_OP_HRB = 22,
     PF_OP_FUSEUP = 23,
     PF_OP_MBX = 24,

@@ -1,4 +1,4 @@
-"""Fused encoder blocks (csrc/k_mbconv.h, expdw epilogue of csrc/k_conv_gemm.h) against the layer-by-layer
+"""Fused encoder blocks (csrc/k_mbconv.h, expdw epilogue of csrc/k_expdw.h) against the layer-by-layer
 program of the same weights and against the oracle.
 
 The fused program replaces, per inverted-residual block (timm InvertedResidual, Student encoder

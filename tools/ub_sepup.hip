@@ -125,21 +125,14 @@ int main(int argc, char** argv) {
     if (g_dbg) printf("ABLATION dbg = %d (results are wrong by construction)\n", g_dbg);
     run_shape<128, 64>("up2 (280 -> 128 at 64 x 64)", Shape{64, 256, 24, 128}, B, [&](auto run) {
         run("shipped <128,64,D=3,W by consumers,defer>", sepup_pipe_kernel<128, 64, 3, false, true>);
-        run("patch requests by consumers", sepup_pipe_kernel<128, 64, 3, false, true, true, false>);
-        run("D=4 (bias in registers)", sepup_pipe_kernel<128, 64, 4, false, true, false, true>);
-        run("D=4 + patch requests by consumers", sepup_pipe_kernel<128, 64, 4, false, true, true, true>);
-        run("D=3, bias in registers only", sepup_pipe_kernel<128, 64, 3, false, true, false, true>);
         run("weights by producers", sepup_pipe_kernel<128, 64, 3, true, true>);
         run("no deferred stores", sepup_pipe_kernel<128, 64, 3, false, false>);
-        run("VCOL", sepup_pipe_kernel<128, 64, 3, false, true, false, false, true>);
-        run("VCOL + D=4", sepup_pipe_kernel<128, 64, 4, false, true, false, true, true>);
+        run("VCOL", sepup_pipe_kernel<128, 64, 3, false, true, true>);
     });
     run_shape<256, 32>("up1 (296 -> 256 at 32 x 32)", Shape{32, 256, 40, 256}, B, [&](auto run) {
         run("shipped <256,32,D=2,W by producers>", sepup_pipe_kernel<256, 32, 2, true, false>);
         run("weights by consumers", sepup_pipe_kernel<256, 32, 2, false, false>);
-        run("patch requests by consumers", sepup_pipe_kernel<256, 32, 2, true, false, true, false>);
-        run("all requests by consumers", sepup_pipe_kernel<256, 32, 2, false, false, true, false>);
-        run("VCOL", sepup_pipe_kernel<256, 32, 2, true, false, false, false, true>);
+        run("VCOL", sepup_pipe_kernel<256, 32, 2, true, false, true>);
     });
     return 0;
 }

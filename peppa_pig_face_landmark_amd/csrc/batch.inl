@@ -160,19 +160,15 @@ static int batch_run_front(pf_batch* b, const uint8_t* frames, int n_frames, int
     const size_t faces = (size_t)n_frames * top_k;
     if (faces > b->sel_cap || (size_t)n_frames > b->sel_cap_frames) {      // (re)allocation: nothing may be in flight on the old buffers
         if (pf_batch_sync(b)) return 1;
+        for (int i = 0; i < L; ++i)      // every lane's tail reads them; realloc_dev tells the front engine, which writes them
+            if (b->lane[i]->graphs.note_realloc(b->lane[i]->err)) PF_BFAIL(b, "lane %d: %s", i, pf_last_error(b->lane[i]));
         const size_t cf = std::max(faces, b->sel_cap), cn = std::max((size_t)n_frames, b->sel_cap_frames);
-        for (int par = 0; par < 2; ++par) {
-            if (b->d_sel_boxes[par]) (void)hipFree(b->d_sel_boxes[par]);
-            if (b->d_sel_count[par]) (void)hipFree(b->d_sel_count[par]);
-            b->d_sel_boxes[par] = nullptr; b->d_sel_count[par] = nullptr;
-            if (hipMalloc((void**)&b->d_sel_boxes[par], cf * 4 * sizeof(float)) != hipSuccess ||
-                hipMalloc((void**)&b->d_sel_count[par], cn * sizeof(int)) != hipSuccess) {
+        for (int par = 0; par < 2; ++par)
+            if (realloc_dev(fr, b->d_sel_boxes[par], cf * 4 * sizeof(float)) || realloc_dev(fr, b->d_sel_count[par], cn * sizeof(int))) {
                 b->sel_cap = b->sel_cap_frames = 0;
-                PF_BFAIL(b, "pf_batch_run_frames: cannot allocate the selected-box buffers");
+                PF_BFAIL(b, "pf_batch_run_frames: cannot allocate the selected-box buffers: %s", pf_last_error(fr));
             }
-        }
         b->sel_cap = cf; b->sel_cap_frames = cn;
-        // graphs captured over the old pointers carry them in their keys and are never matched again
     }
     const int par = (int)(b->front_calls++ & 1);
     float* sel_boxes = b->d_sel_boxes[par];
@@ -182,25 +178,13 @@ static int batch_run_front(pf_batch* b, const uint8_t* frames, int n_frames, int
         for (int i = 0; i < L; ++i)
             if (hipStreamWaitEvent(fr->stream, b->ev_lane[par][i], 0) != hipSuccess) PF_BFAIL(b, "pf_batch_run_frames: hipStreamWaitEvent failed");
     begin_call(fr);
-    {
-        auto enq = [&]() {
+    const GraphKey front_key = GraphKey::front(frames, det_rows, n_frames, height, width, rows, score_thres, iou_thres, min_face, top_k, sel_boxes, sel_count);
+    if (fr->graphs.run(!fr->profiling, fr->stream, fr->err, front_key, [&]() {
             return enqueue_front(fr, frames, n_frames, height, width, det_rows, true, rows, score_thres, iou_thres, min_face, top_k, sel_boxes, sel_count);
-        };
-        int rc;
-        if (fr->use_graphs && !fr->profiling) {
-            GraphKey key{};
-            key.p[0] = frames; key.p[1] = det_rows; key.p[2] = sel_boxes; key.p[3] = sel_count;
-            key.i[0] = n_frames; key.i[1] = height; key.i[2] = width; key.i[3] = rows; key.i[4] = top_k; key.i[5] = 1;
-            key.f[0] = score_thres; key.f[1] = iou_thres; key.f[2] = min_face;
-            rc = graphed_call(fr, key, enq);
-        } else {
-            rc = enq();
-        }
-        if (rc) {
-            b->err = std::string("front engine: ") + pf_last_error(fr);
-            (void)pf_sync(fr);
-            return 1;
-        }
+        })) {
+        b->err = std::string("front engine: ") + pf_last_error(fr);
+        (void)pf_sync(fr);
+        return 1;
     }
     if (hipEventRecord(b->ev_front[par], fr->stream) != hipSuccess) PF_BFAIL(b, "pf_batch_run_frames: hipEventRecord failed");
     for (int i = 0; i < L; ++i) {
@@ -216,17 +200,11 @@ static int batch_run_front(pf_batch* b, const uint8_t* frames, int n_frames, int
             float* ob = boxes ? boxes + (size_t)f0 * n_box : nullptr;
             float* ok = kps ? kps + (size_t)f0 * n_kps : nullptr;
             float* os = scores ? scores + (size_t)f0 * n_sc : nullptr;
-            auto enq = [&]() {
-                return enqueue_tail(h, fp, nf, height, width, sel_boxes + (size_t)f0 * n_box, sel_count + f0, top_k, oc, ob, ok, os, lane_out);
-            };
-            if (h->use_graphs && !h->profiling) {
-                GraphKey key{};
-                key.p[0] = fp; key.p[1] = sel_boxes + (size_t)f0 * n_box; key.p[2] = oc; key.p[3] = ob; key.p[4] = ok; key.p[5] = os;
-                key.i[0] = nf; key.i[1] = height; key.i[2] = width; key.i[3] = lane_out; key.i[4] = top_k; key.i[5] = 2;
-                rc = graphed_call(h, key, enq);
-            } else {
-                rc = enq();
-            }
+            const float* lane_boxes = sel_boxes + (size_t)f0 * n_box; const int* lane_count = sel_count + f0;
+            const GraphKey key = GraphKey::lane_tail(fp, nf, height, width, lane_boxes, lane_count, top_k, oc, ob, ok, os, lane_out);
+            rc = h->graphs.run(!h->profiling, h->stream, h->err, key, [&]() {
+                return enqueue_tail(h, fp, nf, height, width, lane_boxes, lane_count, top_k, oc, ob, ok, os, lane_out);
+            });
         }
         if (!rc && hipEventRecord(b->ev_lane[par][i], h->stream) != hipSuccess) { h->err = "hipEventRecord failed"; rc = 1; }
         if (rc) {

@@ -77,10 +77,9 @@ struct Program {
 
 struct ProfEntry { double ms = 0; int count = 0; };
 
-struct GraphKey { const void* p[6]; int i[6]; float f[3]; unsigned long long epoch; };      // i[5]: 0 whole pf_run_frames call, 1 front half, 2 tail half (pipeline.inl)
-struct GraphEntry { GraphKey key; hipGraphExec_t exec; };
-
 }  // namespace
+
+#include "graph_cache.inl"
 
 struct pf_handle {
     int device = 0;
@@ -93,14 +92,7 @@ struct pf_handle {
     size_t stage_bytes = 0;
     // pipeline scratch (k_prepost)
     PipelineScratch pipe;
-    // hipGraph replay of pf_run_frames* (PF_OPT_HIP_GRAPH)
-    bool use_graphs = false, capturing = false;
-    std::vector<GraphEntry> graphs;
-    // bumped whenever a device allocation a captured graph may reference is (re)made -- scratch growth, program
-    // (re)load -- so that stale graphs are destroyed instead of replayed over freed memory
-    unsigned long long alloc_epoch = 0;
-    // kernel-variant switches for A/B timing on the GPU (environment, read once at pf_create): PEPPA_SEPUP=patch
-    // selects the previous LDS-class-filter decoder front end instead of the register-blocked one
+    GraphCache graphs;       // hipGraph replay of pf_run_frames* and of a pf_batch's halves (graph_cache.inl)
     unsigned long long* d_dbg = nullptr;   // PEPPA_DBG & 64: cycle accounting of sepup_pipe_kernel
     int dbg = 0;             // PEPPA_DBG: timing ablations of the GEMM kernels (ConvGemmArgs::dbg), never set in production
     // tracking state of the handle's video stream (pf_track_frame: one slot) and of its pf_track_streams pool (k_track.h)
@@ -420,7 +412,7 @@ void pf_destroy(pf_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (auto& g : h->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    h->graphs.destroy_all();
     comm_release(h);
     for (auto& p : h->prog) {
         if (p.d_const) (void)hipFree(p.d_const);
@@ -507,10 +499,10 @@ int pf_load_program(pf_handle* h, int slot, const void* blob, size_t bytes, int 
     if (bytes < need) PF_FAIL(h, "program blob truncated (tables)");
     Program& p = h->prog[slot];
     PF_HIP(h, hipStreamSynchronize(h->stream));
+    if (h->graphs.note_realloc(h->err)) return 1;      // graphs captured over the old arena / constants must not be replayed
     if (p.d_const) { (void)hipFree(p.d_const); p.d_const = nullptr; }
     if (p.d_arena) { (void)hipFree(p.d_arena); p.d_arena = nullptr; }
     if (p.d_range) { (void)hipFree(p.d_range); p.d_range = nullptr; }
-    h->alloc_epoch++;            // graphs captured over the old arena / constants must not be replayed
     p.loaded = false;
     p.hdr = hd;
     p.esize = hd.dtype == PF_DTYPE_F16 ? 2 : 4;

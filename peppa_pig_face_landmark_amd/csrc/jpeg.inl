@@ -520,14 +520,7 @@ static int jpeg_decode_batch(pf_handle* h, int n, const uint8_t* const* jpegs, c
         sl.pack_cap = frame_pack * n;
     }
     const size_t out_bytes = (size_t)hd.H * hd.W * 3 * n;
-    if (sl.bgr_cap < out_bytes) {
-        PF_HIP(h, hipStreamSynchronize(h->stream));
-        if (sl.d_bgr) (void)hipFree(sl.d_bgr);
-        sl.d_bgr = nullptr; sl.bgr_cap = 0;
-        h->alloc_epoch++;                          // a captured graph may hold the old frame pointer
-        PF_HIP(h, hipMalloc((void**)&sl.d_bgr, out_bytes));
-        sl.bgr_cap = out_bytes;
-    }
+    if (ensure_dev(h, sl.d_bgr, sl.bgr_cap, out_bytes)) return 1;      // a captured graph may hold the old frame pointer
     // ---- entropy decoding: one file per task ------------------------------------------------------------------------------------
     std::vector<const char*> errs((size_t)n, nullptr);
     std::vector<size_t> used((size_t)n, 0);          // bytes of each frame's region that cross PCIe

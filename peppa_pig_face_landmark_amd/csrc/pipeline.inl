@@ -10,26 +10,21 @@ namespace {
 const int kMaxKeep = 1024;   // rows kept per frame after NMS (s_keep capacity of nms_kernel)
 const int kNumPoints = 98;
 
+// Frees and re-makes a device allocation.  Every one made here may be referenced by a captured graph, so the cache is told first.
 template <typename T>
-int ensure_dev(pf_handle* h, T*& ptr, size_t& have_bytes, size_t need_bytes) {
-    if (need_bytes <= have_bytes && ptr) return 0;
-    if (h->capturing) PF_FAIL(h, "internal: device scratch would be reallocated inside a graph capture");
+int realloc_dev(pf_handle* h, T*& ptr, size_t bytes) {
+    if (h->graphs.note_realloc(h->err)) return 1;
     if (ptr) { (void)hipStreamSynchronize(h->stream); (void)hipFree(ptr); }
     ptr = nullptr;
-    have_bytes = 0;
-    h->alloc_epoch++;            // captured graphs may hold the old pointer
-    PF_HIP(h, hipMalloc((void**)&ptr, need_bytes));
-    have_bytes = need_bytes;
+    PF_HIP(h, hipMalloc((void**)&ptr, bytes));
     return 0;
 }
 
 template <typename T>
-int realloc_dev(pf_handle* h, T*& ptr, size_t bytes) {
-    if (h->capturing) PF_FAIL(h, "internal: device scratch would be reallocated inside a graph capture");
-    if (ptr) { (void)hipStreamSynchronize(h->stream); (void)hipFree(ptr); }
-    ptr = nullptr;
-    h->alloc_epoch++;
-    PF_HIP(h, hipMalloc((void**)&ptr, bytes));
+int ensure_dev(pf_handle* h, T*& ptr, size_t& have_bytes, size_t need_bytes) {
+    if (need_bytes <= have_bytes && ptr) return 0;
+    if (realloc_dev(h, ptr, need_bytes)) { if (!ptr) have_bytes = 0; return 1; }
+    have_bytes = need_bytes;
     return 0;
 }
 
@@ -337,61 +332,7 @@ static int enqueue_run_frames(pf_handle* h, const uint8_t* frames, int mem, int 
     return enqueue_tail(h, d_frames, F, height, width, h->pipe.d_sel_boxes, h->pipe.d_sel_count, top_k, counts, boxes, kps, scores, out_mem);
 }
 
-// hipGraph cache of a handle (PF_OPT_HIP_GRAPH): `enqueue` is launched eagerly the first time `key` is seen (which also performs
-// every lazy allocation / constant upload), captured into a hipGraph the second time and replayed from then on.
-extern "C++" {
-template <typename Enqueue>
-static int graphed_call(pf_handle* h, GraphKey key, Enqueue&& enqueue) {
-    key.epoch = h->alloc_epoch;
-    // any (re)allocation since a graph was captured -- scratch growth for a larger call, a program reload -- may have
-    // freed memory the graph's kernel arguments point at: drop every graph captured under an older epoch
-    if (!h->graphs.empty() && h->graphs.front().key.epoch != h->alloc_epoch) {
-        for (auto& g : h->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        h->graphs.clear();
-    }
-    GraphEntry* e = nullptr;
-    for (auto& g : h->graphs)
-        if (memcmp(&g.key, &key, sizeof(key)) == 0) { e = &g; break; }
-    if (!e) {   // first sighting: run eagerly
-        if (h->graphs.size() >= 16) {
-            for (auto& g : h->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-            h->graphs.clear();
-        }
-        GraphEntry ne{};
-        ne.key = key;
-        h->graphs.push_back(ne);
-        const int rc = enqueue();
-        if (h->alloc_epoch != key.epoch) {   // this eager run (re)allocated scratch: older graphs are stale, this entry is not
-            for (auto& g : h->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-            h->graphs.clear();
-            ne.key.epoch = h->alloc_epoch;
-            if (!rc) h->graphs.push_back(ne);
-        } else if (rc) {
-            h->graphs.pop_back();
-        }
-        return rc;
-    }
-    if (!e->exec) {
-        PF_HIP(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-        h->capturing = true;
-        const int rc = enqueue();
-        h->capturing = false;
-        hipGraph_t graph = nullptr;
-        const hipError_t ce = hipStreamEndCapture(h->stream, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return 1; }
-        if (ce != hipSuccess || !graph) PF_FAIL(h, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-        const hipError_t ie = hipGraphInstantiate(&e->exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ie != hipSuccess) { e->exec = nullptr; PF_FAIL(h, "hipGraphInstantiate failed: %s", hipGetErrorString(ie)); }
-    }
-    PF_HIP(h, hipGraphLaunch(e->exec, h->stream));
-    return 0;
-}
-}  // extern "C++"
-
-// With PF_OPT_HIP_GRAPH on and everything device resident, the ~170 launches of one call are captured
-// into a hipGraph the second time the same (pointers, shapes, thresholds) key is seen and replayed from
-// then on: one graph launch instead of ~170 kernel launches (single-frame latency is launch bound).
+// With PF_OPT_HIP_GRAPH on and everything device resident the call goes through the handle's graph cache (graph_cache.inl).
 int pf_run_frames_planted(pf_handle* h, const uint8_t* frames, int mem, int n_frames, int height, int width,
                           const float* det_rows, int rows, float score_thres, float iou_thres,
                           float min_face, int top_k,
@@ -401,27 +342,18 @@ int pf_run_frames_planted(pf_handle* h, const uint8_t* frames, int mem, int n_fr
     // results into page-locked host memory are plain asynchronous copies on the stream: they capture into the graph too
     begin_call(h);
     h->attr_kind = 0;
-    const bool graphable = h->use_graphs && !h->profiling && mem == PF_MEM_DEVICE &&
-                           (out_mem == PF_MEM_DEVICE || out_mem == PF_MEM_HOST_PINNED);
-    if (!graphable) {
-        if (enqueue_run_frames(h, frames, mem, n_frames, height, width, det_rows, rows, score_thres, iou_thres, min_face,
-                               top_k, counts, boxes, kps, scores, out_mem)) return 1;
-        if (out_mem == PF_MEM_HOST) {
-            PF_HIP(h, hipStreamSynchronize(h->stream));
-            if (check_numerics(h)) return 1;
-        }
-        h->attr_kind = 1; h->attr_rows = n_frames * top_k;          // rows [F][top_k], like kps (pf_face_attrs)
-        return 0;
-    }
-    GraphKey key{};
-    key.p[0] = frames; key.p[1] = det_rows; key.p[2] = counts; key.p[3] = boxes; key.p[4] = kps; key.p[5] = scores;
-    key.i[0] = n_frames; key.i[1] = height; key.i[2] = width; key.i[3] = rows; key.i[4] = top_k;
-    key.f[0] = score_thres; key.f[1] = iou_thres; key.f[2] = min_face;
-    if (graphed_call(h, key, [&]() {
+    const bool capturable = !h->profiling && mem == PF_MEM_DEVICE && (out_mem == PF_MEM_DEVICE || out_mem == PF_MEM_HOST_PINNED);
+    const GraphKey key = GraphKey::whole_call(frames, det_rows, n_frames, height, width, rows, score_thres, iou_thres, min_face, top_k,
+                                              counts, boxes, kps, scores, out_mem);
+    if (h->graphs.run(capturable, h->stream, h->err, key, [&]() {
         return enqueue_run_frames(h, frames, mem, n_frames, height, width, det_rows, rows, score_thres, iou_thres, min_face,
                                   top_k, counts, boxes, kps, scores, out_mem);
     })) return 1;
-    h->attr_kind = 1; h->attr_rows = n_frames * top_k;
+    if (out_mem == PF_MEM_HOST) {
+        PF_HIP(h, hipStreamSynchronize(h->stream));
+        if (check_numerics(h)) return 1;
+    }
+    h->attr_kind = 1; h->attr_rows = n_frames * top_k;          // rows [F][top_k], like kps (pf_face_attrs)
     return 0;
 }
 
@@ -435,10 +367,10 @@ int pf_host_free(void* p) { return (!p || hipHostFree(p) == hipSuccess) ? 0 : 1;
 
 int pf_set_option(pf_handle* h, int option, int value) {
     if (!h) return 1;
-    if (option == PF_OPT_HIP_GRAPH) { h->use_graphs = value != 0; return 0; }
+    if (option == PF_OPT_HIP_GRAPH) { h->graphs.enabled = value != 0; return 0; }
     if (option == PF_OPT_RANGE_CHECK) {
         if (value < 0) PF_FAIL(h, "PF_OPT_RANGE_CHECK: value must be >= 0");
-        if ((value > 0) != (h->range_every > 0)) h->alloc_epoch++;      // captured graphs carry the slot pointers: recapture
+        if ((value > 0) != (h->range_every > 0) && h->graphs.note_realloc(h->err)) return 1;      // captured graphs carry the slot pointers: recapture
         h->range_every = value;                                        // 0 = off, anything else = every forward
         return 0;
     }

@@ -183,6 +183,47 @@ def test_bench_shape_96_frames_lanes_graph_pinned_matches_oracle(hip_library, st
 
 
 @pytest.mark.gpu
+def test_graph_replay_equals_eager_across_selected_box_growth(hip_library, student_weights):
+    """The front engine's selected-box buffers are re-allocated when a call brings more frames or a larger top_k; every lane's and
+    the front engine's captured graphs hold pointers into them and must be dropped, not replayed.  Three lanes, graphs on: 5 frames
+    (slices 2, 2, 1), 6 frames of the same buffer (2, 2, 2: lanes 0 and 1 see the frame pointer, frame count and top_k they saw
+    before while the buffers grew), 5 again, 5 with a larger top_k -- each three times (eager, capture, replay) -- bit-identical after
+    every call with the same call on a second batch that never uses graphs."""
+    import torch
+    H, W, rows_n = 270, 480, 1260
+    blob, _ = build_student_program(student_weights, 128, "f32")
+    frames_np, rows_np = _small_inputs(6)
+    dev = torch.device("cuda", 0)
+    frames, rows = torch.from_numpy(frames_np).to(dev), torch.from_numpy(np.ascontiguousarray(rows_np, np.float32)).to(dev)
+
+    def make(graphs):
+        be = _native.BatchEngine(0, 3, hip_library)
+        be.set_option(_native.PF_OPT_HIP_GRAPH, graphs)
+        be.load_program(_native.PF_NET_LANDMARK, blob, 2 * 3)
+        outs = [torch.zeros(6, dtype=torch.int32, device=dev), torch.zeros(6 * 3, 4, device=dev),       # live for the whole test:
+                torch.zeros(6 * 3, 98, 2, device=dev), torch.zeros(6 * 3, 98, device=dev)]               # the keys hold their addresses
+        return be, outs
+
+    def run(be, outs, F, K):
+        for o in outs:
+            o.zero_()                   # a replay that wrote nothing must not pass on the previous call's results
+        torch.cuda.synchronize()
+        be.run_frames_device(frames.data_ptr(), F, H, W, 0.5, 0.3, 100.0, K, d_planted=rows.data_ptr(), rows=rows_n,
+                             d_counts=outs[0].data_ptr(), d_boxes=outs[1].data_ptr(), d_kps=outs[2].data_ptr(), d_scores=outs[3].data_ptr())
+        be.sync()
+        return [outs[0][:F].clone()] + [o[:F * K].clone() for o in outs[1:]]
+
+    graphed, eager = make(1), make(0)
+    for step, (F, K) in enumerate([(5, 2), (6, 2), (5, 2), (5, 3)]):
+        for rep in range(3):
+            want, got = run(*eager, F, K), run(*graphed, F, K)
+            assert want[0].tolist() == [K] * F, (step, rep)
+            assert all(torch.equal(a, b) for a, b in zip(want, got)), (step, rep)
+    graphed[0].close()
+    eager[0].close()
+
+
+@pytest.mark.gpu
 def test_frame_batch_runner_facade(hip_library, student_weights, detector_weights):
     """FrameBatchRunner.run(frames) returns per frame what a fresh FaceAna.run(frame) returns (device path, no tracking)."""
     from peppa_pig_face_landmark_amd.core.api.batch_runner import FrameBatchRunner

@@ -5,6 +5,7 @@
 // over a static activation arena; nothing is allocated on the hot path.
 #include "../../include/peppa_hip.h"
 
+#include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -73,6 +74,10 @@ struct Program {
     }
     char* tensor_ptr(int t) const { return buf_ptr(tens[t].buf) + (size_t)tens[t].coff * esize; }
     const void* cptr(int off) const { return off < 0 ? nullptr : (const void*)(d_const + off); }
+    // optional operands of an op (index < 0 = absent): pointer or nullptr, row stride or 0
+    char* opt_tensor(int t) const { return t < 0 ? nullptr : tensor_ptr(t); }
+    int opt_ld(int t) const { return t < 0 ? 0 : tens[t].ld; }
+    char* opt_buf(int b) const { return b < 0 ? nullptr : buf_ptr(b); }
 };
 
 struct ProfEntry { double ms = 0; int count = 0; };
@@ -93,8 +98,8 @@ struct pf_handle {
     // pipeline scratch (k_prepost)
     PipelineScratch pipe;
     GraphCache graphs;       // hipGraph replay of pf_run_frames* and of a pf_batch's halves (graph_cache.inl)
-    unsigned long long* d_dbg = nullptr;   // PEPPA_DBG & 64: cycle accounting of sepup_pipe_kernel
-    int dbg = 0;             // PEPPA_DBG: timing ablations of the GEMM kernels (ConvGemmArgs::dbg), never set in production
+    unsigned long long* d_dbg = nullptr;   // PF_ACC_CYCLES / PF_ACC_DET_CYCLES: the cycle counters (PF_CYC_* regions, pf_ablate.h; ensure_cycle_counters)
+    int dbg = 0;             // PEPPA_DBG: the PF_ABL_ / PF_SEL_ / PF_ACC_ bits of pf_ablate.h, never set in production
     // tracking state of the handle's video stream (pf_track_frame: one slot) and of its pf_track_streams pool (k_track.h)
     TrackPool track;
     TrackPool streams;
@@ -129,7 +134,7 @@ struct pf_handle {
 
 static std::string g_create_error;
 
-static inline int host_dbg(const pf_handle* h) { return PF_ABLATE ? h->dbg : 0; }   // see pf_common.h: constant 0 in the production library
+static inline int host_dbg(const pf_handle* h) { return PF_ABLATE ? h->dbg : 0; }   // see pf_ablate.h: constant 0 in the production library
 
 namespace { void comm_release(pf_handle* h); }   // comm.inl
 
@@ -164,12 +169,16 @@ constexpr size_t PF_LAUNCH_LOG_CAP = 1 << 16;
     } while (0)
 
 // ---------------------------------------------------------------------------------------------
-// profiling helper: wraps one launch in an event pair when enabled
+// profiling helper: wraps one launch in an event pair when enabled; the tag is a printf format, filled in only then
 struct ProfScope {
     pf_handle* h;
     std::string tag;
-    ProfScope(pf_handle* h_, const char* tag_) : h(h_) {
-        if (h->profiling) { tag = tag_; (void)hipEventRecord(h->ev0, h->stream); }
+    __attribute__((format(printf, 3, 4))) ProfScope(pf_handle* h_, const char* fmt, ...) : h(h_) {
+        if (!h->profiling) return;
+        char buf[96]; va_list ap;
+        va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
+        tag = buf;
+        (void)hipEventRecord(h->ev0, h->stream);
     }
     ~ProfScope() {
         if (!h->profiling) return;
@@ -216,6 +225,54 @@ static void det_pick_tile(int num_cus, int outH, int outW, int S, int max_rows, 
 // row length check the largest index they will produce against that domain instead of trusting the hard-coded tile
 static inline bool pf_div_small_domain_ok(int max_x_exclusive, int d) {
     return d > 0 && max_x_exclusive <= 4096 && (long long)max_x_exclusive <= (1ll << 20) / d;
+}
+
+// Persistent kernels whose work units are faces: cost, in face times, of cutting each of B faces into `ns` units for a grid of
+// `slots` workgroups -- rounds of the grid, the last one counted whole, and 2 % per extra unit for what every unit of a face
+// fetches again.  384 faces on 256 slots are two rounds of faces (the second half empty) but three rounds of half faces.
+static inline double last_round_cost(int B, int ns, int slots) { return (double)pf_div_up(B * ns, slots) / ns + 0.02 * (ns - 1); }
+
+// cycle counters of the ablation build (pf_ablate.h: PF_ACC_* bits, PF_CYC_* regions of pf_handle::d_dbg)
+static int ensure_cycle_counters(pf_handle* h) {
+    if (h->d_dbg) return 0;
+    PF_HIP(h, hipMalloc((void**)&h->d_dbg, PF_CYC_WORDS * sizeof(unsigned long long)));
+    PF_HIP(h, hipMemset(h->d_dbg, 0, PF_CYC_WORDS * sizeof(unsigned long long)));
+    return 0;
+}
+
+static void print_cycle_counters(const pf_handle* h) {      // at pf_destroy
+    std::vector<unsigned long long> w(PF_CYC_WORDS);
+    if (hipMemcpy(w.data(), h->d_dbg, w.size() * sizeof(w[0]), hipMemcpyDeviceToHost) != hipSuccess) return;
+    for (int k = 0; k < PF_CYC_DETUNIT.entries; ++k) {
+        const unsigned long long* q = &w[PF_CYC_DETUNIT.at(k)];
+        if (!q[4]) continue;
+        const double n = (double)q[4];
+        fprintf(stderr, "[det_unit C=%d S=%d] per workgroup (cycles): input+split %.0f | gemm1 %.0f | depthwise %.0f | gemm2+store %.0f  (%.0f workgroups)\n",
+                k % 3 == 0 ? 32 : (k % 3 == 1 ? 64 : 128), k / 3 + 1, q[0] / n, q[1] / n, q[2] / n, q[3] / n, n);
+    }
+    for (int k = 0; k < PF_CYC_HRB.entries; ++k) {
+        const unsigned long long* q = &w[PF_CYC_HRB.at(k)];
+        if (!q[3]) continue;
+        const double n = (double)q[3];
+        fprintf(stderr, "[det_hr_bottleneck CIN=%d] per workgroup (cycles): conv1 %.0f | conv2 %.0f | conv3+store %.0f  (%.0f workgroups)\n", k ? 256 : 64,
+                q[0] / n, q[1] / n, q[2] / n, n);
+    }
+    for (int k = 0; k < PF_CYC_MBX.entries; ++k) {
+        const unsigned long long* q = &w[PF_CYC_MBX.at(k)];
+        if (!q[7]) continue;
+        static const char* shp[4] = {"KS3 k3", "KS4 k3", "KS4 k5", "KS5 k5d2"};
+        const double n = (double)q[7];
+        fprintf(stderr, "[det_mbx %s mode %d] per wave and launch-face (cycles): prologue+expand0 %.0f | project %.0f | wait a %.0f | depthwise %.0f | expand %.0f | wait b %.0f | epilogue %.0f  (%.0f waves)\n",
+                shp[k / 4], k % 4, q[0] / n, q[1] / n, q[2] / n, q[3] / n, q[4] / n, q[5] / n, q[6] / n, n);
+    }
+    for (int k = 0; k < PF_CYC_SEPUP.entries; ++k) {
+        const unsigned long long* q = &w[PF_CYC_SEPUP.at(k)];
+        if (!q[2]) continue;
+        const double steps = (double)q[3] / (double)q[2];          // K steps per wave
+        fprintf(stderr, "[sepup_pipe BN=%d] per wave and K step (cycles): producer dma %.0f work %.0f wait %.0f | consumer dma %.0f mfma %.0f epilogue %.0f wait %.0f  (%.0f steps/wave)\n",
+                k ? 256 : 128, q[9] / (double)q[2] / steps, q[0] / (double)q[2] / steps, q[1] / (double)q[2] / steps, q[4] / (double)q[8] / steps, q[5] / (double)q[8] / steps,
+                q[6] / (double)q[8] / steps, q[7] / (double)q[8] / steps, steps);
+    }
 }
 
 #include "launch_layers.inl"
@@ -375,7 +432,7 @@ int pf_create(int device_id, pf_handle** out) {
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cus >= 8) h->num_cus = cus;
     }
     if constexpr (PF_ABLATE != 0) {      // ablation build only (libpeppa_hip_ablate.so): ablated kernels compute garbage, so the guard is off
-        if (const char* v = getenv("PEPPA_DBG")) { h->dbg = atoi(v); if (h->dbg & 0xffff) h->range_every = 0; }   // bits >= 16 only re-schedule (wave priorities): results stay right, the guard stays on
+        if (const char* v = getenv("PEPPA_DBG")) { h->dbg = atoi(v); if (h->dbg & PF_DBG_GUARD_OFF_MASK) h->range_every = 0; }   // which bits leave results right: pf_ablate.h
         if (const char* v = getenv("PEPPA_DET_TILE")) { if (sscanf(v, "%d,%d", &g_det_tile_th, &g_det_tile_tw) != 2) g_det_tile_th = g_det_tile_tw = 0; }
     }
     bool masked = false;
@@ -422,46 +479,7 @@ void pf_destroy(pf_handle* h) {
     if (h->d_stage) (void)hipFree(h->d_stage);
     if (h->d_attr_valid) (void)hipFree(h->d_attr_valid);
     if (h->d_track_attrs) (void)hipFree(h->d_track_attrs);
-    if (h->d_dbg) {
-        unsigned long long u[48];
-        if (hipMemcpy(u, h->d_dbg + 64, sizeof(u), hipMemcpyDeviceToHost) == hipSuccess) {
-            for (int k = 0; k < 6; ++k) {
-                const unsigned long long* q = u + 8 * k;
-                if (!q[4]) continue;
-                const double n = (double)q[4];
-                fprintf(stderr, "[det_unit C=%d S=%d] per workgroup (cycles): input+split %.0f | gemm1 %.0f | depthwise %.0f | gemm2+store %.0f  (%.0f workgroups)\n",
-                        k % 3 == 0 ? 32 : (k % 3 == 1 ? 64 : 128), k / 3 + 1, q[0] / n, q[1] / n, q[2] / n, q[3] / n, n);
-            }
-        }
-        unsigned long long hb[8];
-        if (hipMemcpy(hb, h->d_dbg + 144, sizeof(hb), hipMemcpyDeviceToHost) == hipSuccess)
-            for (int k = 0; k < 2; ++k)
-                if (hb[4 * k + 3])
-                    fprintf(stderr, "[det_hr_bottleneck CIN=%d] per workgroup (cycles): conv1 %.0f | conv2 %.0f | conv3+store %.0f  (%.0f workgroups)\n", k ? 256 : 64,
-                            hb[4 * k] / (double)hb[4 * k + 3], hb[4 * k + 1] / (double)hb[4 * k + 3], hb[4 * k + 2] / (double)hb[4 * k + 3], (double)hb[4 * k + 3]);
-        unsigned long long mb[128];
-        if (hipMemcpy(mb, h->d_dbg + 160, sizeof(mb), hipMemcpyDeviceToHost) == hipSuccess)
-            for (int k = 0; k < 16; ++k) {
-                const unsigned long long* q = mb + 8 * k;
-                if (!q[7]) continue;
-                static const char* shp[4] = {"KS3 k3", "KS4 k3", "KS4 k5", "KS5 k5d2"};
-                const double n = (double)q[7];
-                fprintf(stderr, "[det_mbx %s mode %d] per wave and launch-face (cycles): prologue+expand0 %.0f | project %.0f | wait a %.0f | depthwise %.0f | expand %.0f | wait b %.0f | epilogue %.0f  (%.0f waves)\n",
-                        shp[k / 4], k % 4, q[0] / n, q[1] / n, q[2] / n, q[3] / n, q[4] / n, q[5] / n, q[6] / n, n);
-            }
-        unsigned long long v[32];
-        if (hipMemcpy(v, h->d_dbg, sizeof(v), hipMemcpyDeviceToHost) == hipSuccess) {
-            for (int k = 0; k < 2; ++k) {
-                const unsigned long long* q = v + 16 * k;
-                if (!q[2]) continue;
-                const double steps = (double)q[3] / (double)q[2];          // K steps per wave
-                fprintf(stderr, "[sepup_pipe BN=%d] per wave and K step (cycles): producer dma %.0f work %.0f wait %.0f | consumer dma %.0f mfma %.0f epilogue %.0f wait %.0f  (%.0f steps/wave)\n",
-                        k ? 256 : 128, q[9] / (double)q[2] / steps, q[0] / (double)q[2] / steps, q[1] / (double)q[2] / steps, q[4] / (double)q[8] / steps, q[5] / (double)q[8] / steps,
-                        q[6] / (double)q[8] / steps, q[7] / (double)q[8] / steps, steps);
-            }
-        }
-        (void)hipFree(h->d_dbg);
-    }
+    if (h->d_dbg) { print_cycle_counters(h); (void)hipFree(h->d_dbg); }
     if (h->h_status) (void)hipHostFree(h->h_status);
     h->pipe.release();
     h->track.release();

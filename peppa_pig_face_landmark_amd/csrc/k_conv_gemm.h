@@ -56,12 +56,8 @@ struct ConvGemmArgs {
     // bias, both BN folded; the depthwise output goes to `out`, its per-face channel means (SE squeeze) to gap_out
     float* gap_out;       // [B][N] or nullptr
     unsigned* range_slot; // f32s range guard: max |v| (raw bits) over everything this launch splits into f16 hi / lo, or nullptr
-    // timing ablations of conv3x3_halo_split_kernel (PEPPA_DBG bit mask, 0 in production; results are WRONG when set):
-    // 1 = weights fetched for the first K step only, 16 = no MFMAs, 32 = no output stores, 64 = input patch staged for the
-    // first channel chunk only, 128 = no per-tap barrier; conv_gemm_split_kernel: 16 as above, 256 = operands (pixels AND weights)
-    // fetched for the first K step only, 512 = no split / LDS store of the pixel operand, 1024 = no depthwise taps in the fused
-    // expand + depthwise epilogue.  Tables: profiles/r02_*ablations.md.
-    int dbg;    // per-tile channel sums of the stored output (GAPP epilogue instances only, conv_gemm_epilogue): [B][nslots][Npad] f32,
+    int dbg;              // PEPPA_DBG bit mask of the ablation build, 0 in production: pf_ablate.h has the table (PF_ABL_* bits)
+    // per-tile channel sums of the stored output (GAPP epilogue instances only, conv_gemm_epilogue): [B][nslots][Npad] f32,
     // nslots = (OHW / BM) * WARPS_M -- slot = (tile of the face, M-wave); the face-attribute head's pools (k_layers.h face_attrs_kernel)
     float* gap_parts;
 };
@@ -174,7 +170,7 @@ __device__ __forceinline__ void conv_gemm_epilogue(const ConvGemmArgs& a, pf_f32
                 for (int r = 0; r < 4; ++r)
                     if (v[r] > best_v[r]) { best_v[r] = v[r]; best_i[r] = local; }
             }
-            if (a.store_out && mok && !(pf_dbg(a) & 32)) {
+            if (a.store_out && mok && !(pf_dbg(a) & PF_ABL_NO_STORE)) {
                 T* o = out + (size_t)m * a.outLd;
                 if (a.outCs == 1 && n + 3 < a.N) {
                     if constexpr (sizeof(T) == 2) {

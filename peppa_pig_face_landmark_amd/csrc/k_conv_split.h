@@ -276,7 +276,7 @@ __global__ __launch_bounds__(WARPS_M * WARPS_N * 64, BN >= 256 ? WARPS_M * WARPS
         if constexpr (MT == 2 && NT >= 4) {
             // wide-N tiles: the two pixel fragments stay live and the weight fragments come one 16-channel tile at a time -- 24
             // fragment registers instead of 8 NT + 8 (same products in the same order per accumulator)
-            if (!(pf_dbg(a) & 16)) {
+            if (!(pf_dbg(a) & PF_ABL_NO_MFMA)) {
                 pf_half8 xhf[MT], xlf[MT];
 #pragma unroll
                 for (int i = 0; i < MT; ++i) {
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(WARPS_M * WARPS_N * 64, BN >= 256 ? WARPS_M * WARPS
             whf[j] = *reinterpret_cast<const pf_half8*>(wh + off);
             wlf[j] = *reinterpret_cast<const pf_half8*>(wl + off);
         }
-        if (!(pf_dbg(a) & 16))
+        if (!(pf_dbg(a) & PF_ABL_NO_MFMA))
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             const int off = pf_lds_chunk_off(wm * WM + i * 16 + frow, fchunk);
@@ -392,10 +392,10 @@ __global__ __launch_bounds__(WARPS_M * WARPS_N * 64, BN >= 256 ? WARPS_M * WARPS
             pf_static_for<NK>([&](auto kt_tag) {
                 constexpr int kt = decltype(kt_tag)::value;
                 constexpr int cur = kt & 1;
-                if constexpr (kt + 1 < NK) { if (!(pf_dbg(a) & 256)) load_w_at(std::integral_constant<int, kt + 1>{}, cur ^ 1); }
-                if constexpr (kt + 2 < NK) { if (!(pf_dbg(a) & 256)) load_x_at(std::integral_constant<int, kt + 2>{}, xreg[cur]); }
+                if constexpr (kt + 1 < NK) { if (!(pf_dbg(a) & PF_ABL_OPERANDS_FIRST_K)) load_w_at(std::integral_constant<int, kt + 1>{}, cur ^ 1); }
+                if constexpr (kt + 2 < NK) { if (!(pf_dbg(a) & PF_ABL_OPERANDS_FIRST_K)) load_x_at(std::integral_constant<int, kt + 2>{}, xreg[cur]); }
                 mma_stage(cur);
-                if constexpr (kt + 1 < NK) { if (!(pf_dbg(a) & 512)) store_tile(cur ^ 1, kt + 1, xreg[cur ^ 1]); }
+                if constexpr (kt + 1 < NK) { if (!(pf_dbg(a) & PF_ABL_NO_SPLIT_STORE)) store_tile(cur ^ 1, kt + 1, xreg[cur ^ 1]); }
                 pf_pin(amax);       // the range guard's running maximum is due NOW: left alone, the compiler keeps every step's eight
                                     // values (in scratch) and folds them at the end of the unrolled loop
                 if constexpr (kt + 2 < NK) pf_wait_vm_barrier<2 * XUNITS>(); else pf_wait_vm_barrier<0>();
@@ -407,9 +407,9 @@ __global__ __launch_bounds__(WARPS_M * WARPS_N * 64, BN >= 256 ? WARPS_M * WARPS
         for (int kt = 0; kt < nk; ++kt) {
             const int cur = kt & 1;
             const bool more = kt + 1 < nk;
-            if (more && !(pf_dbg(a) & 256)) { load_x(kt + 1, xreg[0]); load_w(0, kt + 1, cur ^ 1); }
+            if (more && !(pf_dbg(a) & PF_ABL_OPERANDS_FIRST_K)) { load_x(kt + 1, xreg[0]); load_w(0, kt + 1, cur ^ 1); }
             mma_stage(cur);
-            if (more && !(pf_dbg(a) & 512)) store_tile(cur ^ 1, kt + 1, xreg[0]);
+            if (more && !(pf_dbg(a) & PF_ABL_NO_SPLIT_STORE)) store_tile(cur ^ 1, kt + 1, xreg[0]);
             __syncthreads();
         }
         }
@@ -423,10 +423,10 @@ __global__ __launch_bounds__(WARPS_M * WARPS_N * 64, BN >= 256 ? WARPS_M * WARPS
         const bool more = kt + 1 < nk;
         if (more) {
             if (++tap == taps) { tap = 0; ++cb; }
-            if (!(pf_dbg(a) & 256)) load_tile(tap, cb, cur ^ 1);
+            if (!(pf_dbg(a) & PF_ABL_OPERANDS_FIRST_K)) load_tile(tap, cb, cur ^ 1);
         }
         mma_stage(cur);
-        if (more && !(pf_dbg(a) & 512)) store_tile(cur ^ 1, cb, xreg[0]);
+        if (more && !(pf_dbg(a) & PF_ABL_NO_SPLIT_STORE)) store_tile(cur ^ 1, cb, xreg[0]);
         __syncthreads();
     }
     }

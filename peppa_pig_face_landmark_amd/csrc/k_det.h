@@ -134,7 +134,7 @@ struct DetUnitArgs {
     float s1, s2, s3;     // 2^-s of the three weight sets
     int B, inH, inW, inLd, Cin, outH, outW, outLd, TH, TW, tilesX, tpf;     // tpf: tiles per frame
     unsigned* range_slot;
-    unsigned long long* prof;   // ablation build only (PEPPA_DBG & 4096): [5] cycles of phase 0 / GEMM 1 / depthwise / last GEMMs, workgroups
+    unsigned long long* prof;   // ablation build only (PF_ACC_DET_CYCLES, an entry of PF_CYC_DETUNIT): [5] cycles of phase 0 / GEMM 1 / depthwise / last GEMMs, workgroups
 };
 
 // WPS: waves per SIMD the register allocation must leave room for (workgroups per CU x NTHR / 256)

@@ -77,7 +77,7 @@ __device__ __forceinline__ void expdw_epilogue(const ConvGemmArgs& a, pf_f32x4 (
 #pragma unroll
         for (int ky = 0; ky < K; ++ky) {
             const int yy = row + ky * DIL - PAD;
-            if ((unsigned)yy >= 16u || (pf_dbg(a) & 1024)) continue;
+            if ((unsigned)yy >= 16u || (pf_dbg(a) & PF_ABL_EXPDW_NO_DW_TAPS)) continue;
             const float* erow = es + (yy * 16) * ES + c2;
             pf_f32x2 in[16];
 #pragma unroll
@@ -100,7 +100,7 @@ __device__ __forceinline__ void expdw_epilogue(const ConvGemmArgs& a, pf_f32x4 (
         const int m = m0 + row * 16;
         pf_f32x2 rs = pf_f32x2{0.f, 0.f};
         float* out = static_cast<float*>(a.out);
-        if (m < M && !(pf_dbg(a) & 32)) {
+        if (m < M && !(pf_dbg(a) & PF_ABL_NO_STORE)) {
 #pragma unroll
             for (int x = 0; x < 16; ++x) {
                 float* po = out + (size_t)(m + x) * a.outLd + n2;

@@ -131,13 +131,13 @@ __global__ __launch_bounds__(WARPS_M * WARPS_N * 64, WARPS_M * WARPS_N / 2) void
         const int cur = kt & 1;
         const bool more = kt + 1 < nk;
         const bool last_tap = tap == 8;
-        if (more && !(pf_dbg(a) & 1)) load_w(last_tap ? 0 : tap + 1, last_tap ? cb + 1 : cb, cur ^ 1);
-        if (tap == 0 && cb + 1 < cblocks && !(pf_dbg(a) & 64)) load_x(cb + 1);          // next chunk's patch: nine taps of latency cover
+        if (more && !(pf_dbg(a) & PF_ABL_W_FIRST_K)) load_w(last_tap ? 0 : tap + 1, last_tap ? cb + 1 : cb, cur ^ 1);
+        if (tap == 0 && cb + 1 < cblocks && !(pf_dbg(a) & PF_ABL_PATCH_FIRST_CHUNK)) load_x(cb + 1);          // next chunk's patch: nine taps of latency cover
         const unsigned char* wh = wbase + cur * W_BYTES;
         const unsigned char* wl = wh + BN * 64;
         const int ky = tap / 3, kx = tap - ky * 3;
         const int shift = ky * HW2 + kx;
-        if (!(pf_dbg(a) & 16)) {
+        if (!(pf_dbg(a) & PF_ABL_NO_MFMA)) {
             if constexpr (MT == 2) {
                 // pixel fragments of the (two) 16-pixel sub-tiles stay live, weight fragments come one 16-channel tile at a
                 // time: 24 fragment registers instead of 40, which is what keeps this kernel out of scratch at 128 VGPRs
@@ -182,11 +182,11 @@ __global__ __launch_bounds__(WARPS_M * WARPS_N * 64, WARPS_M * WARPS_N / 2) void
                 }
             }
         }
-        if (last_tap && more && !(pf_dbg(a) & 64)) {
+        if (last_tap && more && !(pf_dbg(a) & PF_ABL_PATCH_FIRST_CHUNK)) {
             __syncthreads();                 // every wave is done with this chunk's patch
             store_x();
         }
-        if (!(pf_dbg(a) & 128)) __syncthreads();
+        if (!(pf_dbg(a) & PF_ABL_HALO_NO_TAP_BARRIER)) __syncthreads();
         if (last_tap) { tap = 0; ++cb; } else ++tap;
     }
     pf_amax_commit(a.range_slot, amax, amax_seen);

@@ -29,7 +29,7 @@ struct HrbArgs {
     float s1, s2, s3, sd;
     int B, H, W, xLd, outLd, TR, TW, tiles_x, tpf;      // tile = TR rows x TW columns; tpf = tiles per face
     unsigned* range_slot;
-    unsigned long long* prof;   // ablation build only (PEPPA_DBG & 4096): cycles of conv1 / conv2 / conv3 [3], workgroups
+    unsigned long long* prof;   // ablation build only (PF_ACC_DET_CYCLES, an entry of PF_CYC_HRB): cycles of conv1 / conv2 / conv3 [3], workgroups
 };
 
 template <int CIN, bool DS, int MAXR, int MAXP, int ITX>

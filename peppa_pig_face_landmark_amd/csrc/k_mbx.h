@@ -152,7 +152,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mbx_kernel(MbxArgs a) {
         }
     };
 
-    const bool prof = (pf_dbg(a) & 64) != 0;
+    const bool prof = (pf_dbg(a) & PF_ACC_CYCLES) != 0;
     unsigned long long c_pro = 0, c_mma = 0, c_wa = 0, c_dw = 0, c_exp = 0, c_wb = 0, c_epi = 0;
     const int NS = SQUEEZE ? a.nsplit : 1;
     for (int unit = blockIdx.x; unit < a.B * NS; unit += gridDim.x) {
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mbx_kernel(MbxArgs a) {
                         eq[(step + 1) & 1][1] = *reinterpret_cast<const pf_half8*>(wsrc + 2048 + off);
                     }
                     const pf_half8 wh = eq[step & 1][0], wl = eq[step & 1][1];
-                    if (pf_dbg(a) & 4) continue;
+                    if (pf_dbg(a) & PF_ABL_MBX_NO_MFMA) continue;
 #pragma unroll
                     for (int i = 0; i < MT; ++i) acc[i][j] = pf_mfma_16x16x32_f16(wl, xh[i][s], acc[i][j]);      // small terms first
 #pragma unroll
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mbx_kernel(MbxArgs a) {
                         wq[(j + 1) & 1][1] = *reinterpret_cast<const pf_half8*>(w2s + COUT * 64 + off);
                     }
                     const pf_half8 wh = wq[j & 1][0], wl = wq[j & 1][1];
-                    if (pf_dbg(a) & 4) continue;
+                    if (pf_dbg(a) & PF_ABL_MBX_NO_MFMA) continue;
 #pragma unroll
                     for (int i = 0; i < MT; ++i) oacc[i][j] = pf_mfma_16x16x32_f16(wl, dh[i], oacc[i][j]);     // small terms first
 #pragma unroll
@@ -335,7 +335,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mbx_kernel(MbxArgs a) {
                 for (int kx = 0; kx < K; ++kx) {
                     pf_f32x2 w = *reinterpret_cast<const pf_f32x2*>(ct + (ky * K + kx) * 32 + c2);
                     if constexpr (!ROW_UNIFORM) { if (!yok) w = pf_f32x2{0.f, 0.f}; }      // a filter row above / below the image: its taps contribute nothing
-                    if (pf_dbg(a) & 2) continue;
+                    if (pf_dbg(a) & PF_ABL_MBX_NO_DW_TAPS) continue;
 #pragma unroll
                     for (int x = 0; x < XP; ++x) {
                         of[2 * x] = fmaf(w[0], in[x + kx * DIL][0], of[2 * x]);
@@ -352,7 +352,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mbx_kernel(MbxArgs a) {
                 *reinterpret_cast<pf_f32x2*>(psum + (tile & 1) * (NPART * 32) + (yrow * NP + part) * 32 + c2) = rs;
                 if constexpr (STORE_D) {                    // a pixel's 32 channels of the tile are one 128-byte line: 16 lanes x 8 bytes
                     float* drow = a.out + ((size_t)face * 256 + yrow * 16 + XP * part) * a.outLd + (tb + tile) * 32 + c2;
-                    if ((tb + tile) * 32 + c2 < a.CEXP && !(pf_dbg(a) & 16))
+                    if ((tb + tile) * 32 + c2 < a.CEXP && !(pf_dbg(a) & PF_ABL_MBX_NO_STORE))
 #pragma unroll
                         for (int x = 0; x < XP; ++x) *reinterpret_cast<pf_f32x2*>(drow + (size_t)x * a.outLd) = pf_f32x2{of[2 * x], of[2 * x + 1]};
                 }
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mbx_kernel(MbxArgs a) {
             for (int tile = 0; tile < T; ++tile) {
                 // ======== phase a: project(tile - 1) | depthwise of tile -> D[tile & 1]; W1 / constants of tile + 1 on their way ==============
                 const unsigned long long q1 = prof ? pf_clock() : 0;
-                if (tile + 1 < T && !((pf_dbg(a) & 1) && tile > 0)) { dma_w1(tile + 1); dma_ct(tile + 1, face); }
+                if (tile + 1 < T && !((pf_dbg(a) & PF_ABL_MBX_DMA_FIRST_TILE) && tile > 0)) { dma_w1(tile + 1); dma_ct(tile + 1, face); }
                 unsigned long long q2 = q1, q3 = q1;
                 if (wave < NW / 2) {
                     if (tile >= 1) project(tile - 1);
@@ -418,7 +418,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mbx_kernel(MbxArgs a) {
                 pf_wait_vm_barrier<0>();
                 // ======== phase b: expand(tile + 1) -> E; W2 of tile on its way =============================================================
                 const unsigned long long q4 = prof ? pf_clock() : 0;
-                if (!((pf_dbg(a) & 1) && tile > 0)) dma_w2(tile);
+                if (!((pf_dbg(a) & PF_ABL_MBX_DMA_FIRST_TILE) && tile > 0)) dma_w2(tile);
                 if (tile + 1 < T) expand(tile + 1);
                 const unsigned long long q6 = prof ? pf_clock() : 0;
                 pf_wait_vm_barrier<0>();
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mbx_kernel(MbxArgs a) {
             for (int tile = 0; tile < T; ++tile) {
                 // ======== one phase: expand(tile + 1) -> E[(tile + 1) & 1] | depthwise of tile; W1 / constants of tile + 2 on their way ==========
                 const unsigned long long q1 = prof ? pf_clock() : 0;
-                if (tile + 2 < T && !((pf_dbg(a) & 1) && tile > 0)) { dma_w1(tile + 2); dma_ct(tile + 2, face); }
+                if (tile + 2 < T && !((pf_dbg(a) & PF_ABL_MBX_DMA_FIRST_TILE) && tile > 0)) { dma_w1(tile + 2); dma_ct(tile + 2, face); }
                 unsigned long long q2 = q1, q3 = q1;
                 if (wave < NW / 2) {
                     if (tile + 1 < T) expand(tile + 1);
@@ -465,7 +465,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mbx_kernel(MbxArgs a) {
             }
             project(T - 1);
             float* __restrict__ orow = a.out + ((size_t)face * 256 + wv * 16 * MT + pcol) * a.outLd + kg * 4;
-            if (!(pf_dbg(a) & 16))
+            if (!(pf_dbg(a) & PF_ABL_MBX_NO_STORE))
 #pragma unroll
             for (int j = 0; j < NTO; ++j) {
                 const pf_f32x4 bv = *reinterpret_cast<const pf_f32x4*>(a.b2 + j * 16 + kg * 4);

@@ -18,9 +18,8 @@ struct MbxArgs {
                                // faces on 256 CUs are two rounds of whole faces but three of half faces (1.5 instead of 2 face times); 1 otherwise
     float scale1, scale2;      // 1 / (power-of-two weight scales)
     unsigned* range_slot;
-    unsigned long long* prof;  // ablation build, dbg & 64: per-wave cycle totals {prologue + expand(0), project, wait a, depthwise, expand, wait b, epilogue, waves}
-    int dbg;                   // timing ablations (ablation build only; results are WRONG when set): 1 no DMA after the first tile, 2 no depthwise
-                               // taps, 4 no MFMAs, 16 no output stores
+    unsigned long long* prof;  // ablation build, dbg & PF_ACC_CYCLES: an entry of PF_CYC_MBX, per-wave cycle totals {prologue + expand(0), project, wait a, depthwise, expand, wait b, epilogue, waves}
+    int dbg;                   // PEPPA_DBG (pf_ablate.h): PF_ABL_MBX_DMA_FIRST_TILE, _NO_DW_TAPS, _NO_MFMA, _NO_STORE, PF_ACC_CYCLES
 };
 
 

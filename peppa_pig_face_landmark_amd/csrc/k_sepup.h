@@ -50,8 +50,8 @@ struct SepupArgs {
     float* gap_part;            // [B * tiles per face][N] or nullptr: per-tile channel sums of the ACTIVATED output (the squeeze of the SCSE block
                                 //                        that follows, model.py:117-130): the consumers have every output of a tile in registers
     unsigned* range_slot;       // f32s range guard: max |v| (raw bits) over the depthwise outputs both kernels split, or nullptr
-    unsigned long long* prof;   // dbg & 64: per-role cycle totals {producer: work, barrier wait | consumer: dma issue, mfma, epilogue, barrier wait} + wave counts
-    int dbg;                    // timing ablations (1 no weight refresh, 2 no patch/filter refresh, 4 no producer taps, 8 no MFMAs, 16 no stores)
+    unsigned long long* prof;   // dbg & PF_ACC_CYCLES: an entry of PF_CYC_SEPUP, per-role cycle totals {producer: work, barrier wait | consumer: dma issue, mfma, epilogue, barrier wait} + wave counts
+    int dbg;                    // PEPPA_DBG (pf_ablate.h): PF_ABL_SEPUP_NO_W_DMA, _NO_P_DMA, _NO_PATCH_READS, _NO_MFMA, _NO_STORE, PF_ACC_CYCLES
 };
 
 // ---- depthwise 3x3 of the skip-connection channels, written as ready-made pixel-operand stages -------------------------
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
     const int NK = a.Cpad >> 5, lo_chunks = a.C1 >> 5, nskip = NK - lo_chunks;
     const int S = nt * NK;                               // K steps of this workgroup, all tiles
     const size_t wrow_bytes = (size_t)NK * 128;
-    const bool prof = (pf_dbg(a) & 64) != 0;
+    const bool prof = (pf_dbg(a) & PF_ACC_CYCLES) != 0;
 
     for (int i = t; i < BN; i += 1024) sbias[i] = a.bias[i];
 
@@ -304,8 +304,8 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
             const unsigned long long c0 = prof ? pf_clock() : 0;
             // requests of this iteration: the stage read D - 1 steps from now and (W_BY_PROD) the weights consumed D - 1 iterations from now
             int nreq = 0;
-            if (issued_p < S && !(pf_dbg(a) & 2)) { dma_issue(issued_p % D); ++issued_p; nreq += PI; }
-            if (W_BY_PROD && g >= 1 && issued_w < S && !(pf_dbg(a) & 1)) { w_issue(issued_w); ++issued_w; nreq += WI; }
+            if (issued_p < S && !(pf_dbg(a) & PF_ABL_SEPUP_NO_P_DMA)) { dma_issue(issued_p % D); ++issued_p; nreq += PI; }
+            if (W_BY_PROD && g >= 1 && issued_w < S && !(pf_dbg(a) & PF_ABL_SEPUP_NO_W_DMA)) { w_issue(issued_w); ++issued_w; nreq += WI; }
             const unsigned long long c1 = prof ? pf_clock() : 0;
             if (g < S) {
                 const unsigned char* pst = pbase + (g % D) * P_BYTES;
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
 #pragma unroll
                         for (int r = 0; r < 3; ++r) {
                             pf_f32x2 p0 = pf_f32x2{0.f, 0.f}, p1 = p0, p2 = p0;
-                            if (!(pf_dbg(a) & 4)) {
+                            if (!(pf_dbg(a) & PF_ABL_SEPUP_NO_PATCH_READS)) {
                                 p0 = *reinterpret_cast<const pf_f32x2*>(pa + (r * PC + 0) * 128);
                                 p1 = *reinterpret_cast<const pf_f32x2*>(pa + (r * PC + 1) * 128);
                                 p2 = *reinterpret_cast<const pf_f32x2*>(pa + (r * PC + 2) * 128);
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
         auto store_vec = [&](float* orow, int k, pf_f32x4 v) {      // vector k = (channel tile j = k >> 1, pixel half i = k & 1)
             const int n = wn * WN + (k >> 1) * 16 + crow;
             const int m = wm * 32 + (k & 1) * 16 + frow;
-            if (n < a.N && !(pf_dbg(a) & 16)) *reinterpret_cast<pf_f32x4*>(orow + (size_t)m * a.outLd + n) = v;
+            if (n < a.N && !(pf_dbg(a) & PF_ABL_SEPUP_NO_STORE)) *reinterpret_cast<pf_f32x4*>(orow + (size_t)m * a.outLd + n) = v;
         };
         int cj = 0, ccb = 0;                                        // consume position
         int gap_gt = -1;                                            // GAP_OK: global tile whose partial sums wait in LDS
@@ -457,7 +457,7 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
             }
             if (g >= 1) {
                 const int c = g - 1;
-                if (!W_BY_PROD && issued_w < S && !(pf_dbg(a) & 1)) { w_issue(issued_w); ++issued_w; nreq += WI; }
+                if (!W_BY_PROD && issued_w < S && !(pf_dbg(a) & PF_ABL_SEPUP_NO_W_DMA)) { w_issue(issued_w); ++issued_w; nreq += WI; }
                 if (prof) c1 = pf_clock();
                 const unsigned char* xs = xbase + (c & 1) * X_BYTES;
                 const unsigned char* wh = wbase + (c % D) * W_BYTES;
@@ -467,7 +467,7 @@ __global__ __launch_bounds__(1024, 4) void sepup_pipe_kernel(SepupArgs a) {
                 xlf[0] = *reinterpret_cast<const pf_half8*>(xs + 8192 + xoff0);
                 xhf[1] = *reinterpret_cast<const pf_half8*>(xs + xoff1);
                 xlf[1] = *reinterpret_cast<const pf_half8*>(xs + 8192 + xoff1);
-                if (!(pf_dbg(a) & 8))
+                if (!(pf_dbg(a) & PF_ABL_SEPUP_NO_MFMA))
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
                     const int off = pf_lds_chunk_off(wn * WN + j * 16 + frow, fchunk);

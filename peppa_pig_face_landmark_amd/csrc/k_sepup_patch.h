@@ -134,7 +134,7 @@ __global__ __launch_bounds__(WARPS_M * WARPS_N * 64, BN >= 256 ? WARPS_M * WARPS
     if (lo_chunks > 1) load_patch(1);
     for (int cb = 0; cb < cblocks; ++cb) {
         // ---- phase 1: weights of this step || produce the pixel operand ----------------------------------------
-        if (!(pf_dbg(a) & 1) || cb == 0) dma_weights(cb);
+        if (!(pf_dbg(a) & PF_ABL_W_FIRST_K) || cb == 0) dma_weights(cb);
         float o[8];
         const int kelem = cb * 32 + xc * 8;
 #pragma unroll
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(WARPS_M * WARPS_N * 64, BN >= 256 ? WARPS_M * WARPS
             for (int e = 0; e < 4; ++e) { o[e] = b0[e]; o[4 + e] = b1[e]; }
             if (cb < lo_chunks) {
 #pragma unroll 1
-                for (int j = 0; j < ((pf_dbg(a) & 256) ? 1 : 3); ++j)   // one patch row at a time keeps the live LDS reads (and VGPRs) bounded
+                for (int j = 0; j < ((pf_dbg(a) & PF_ABL_PATCH_ONE_ROW) ? 1 : 3); ++j)   // one patch row at a time keeps the live LDS reads (and VGPRs) bounded
 #pragma unroll
                     for (int i = 0; i < 3; ++i) {
                         const float* pp = ppix + (j * PC + i) * 32;
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(WARPS_M * WARPS_N * 64, BN >= 256 ? WARPS_M * WARPS
         }
         __syncthreads();
         // ---- phase 2: next chunk's patch and filters || MFMAs -------------------------------------------------------
-        if (cb + 1 < lo_chunks && !(pf_dbg(a) & 64)) {
+        if (cb + 1 < lo_chunks && !(pf_dbg(a) & PF_ABL_PATCH_FIRST_CHUNK)) {
             store_patch();
             dma_filters(cb + 1);
             if (cb + 2 < lo_chunks) load_patch(cb + 2);

@@ -14,17 +14,14 @@ static int launch_detunit(pf_handle* h, const Program& p, const PfDetunitOp& o, 
     a.Cin = o.Cin;
     a.B = B; a.inH = ti.H; a.inW = ti.W; a.inLd = ti.ld; a.outH = to.H; a.outW = to.W; a.outLd = to.ld;
     a.range_slot = range_slot;
-    if (host_dbg(h) & 4096) {      // per-phase cycle accounting of det_unit_kernel (ablation build; printed at pf_destroy)
-        if (!h->d_dbg) { PF_HIP(h, hipMalloc((void**)&h->d_dbg, 64 * 16 * sizeof(unsigned long long))); PF_HIP(h, hipMemset(h->d_dbg, 0, 64 * 16 * sizeof(unsigned long long))); }
-        a.prof = h->d_dbg + 64 + 8 * ((C == 32 ? 0 : (C == 64 ? 1 : 2)) + 3 * (S - 1));
+    if (host_dbg(h) & PF_ACC_DET_CYCLES) {      // per-phase cycle accounting of det_unit_kernel (ablation build; printed at pf_destroy)
+        if (ensure_cycle_counters(h)) return 1;
+        a.prof = h->d_dbg + PF_CYC_DETUNIT.at((C == 32 ? 0 : (C == 64 ? 1 : 2)) + 3 * (S - 1));
     }
     if (to.C != 2 * C || ti.C != a.Cin || (S != 1 && S != 2) || to.H != (ti.H - 1) / S + 1 || to.W != (ti.W - 1) / S + 1 ||
         (S == 1 && a.Cin != 2 * C) || (S == 2 && !a.w3))
         PF_FAIL(h, "detunit: inconsistent shapes");
-    char tagbuf[96];
-    tagbuf[0] = 0;
-    if (h->profiling) snprintf(tagbuf, sizeof(tagbuf), "unit_s%d_c%d_%dx%d", S, C, to.H, to.W);
-    ProfScope ps(h, tagbuf);
+    ProfScope ps(h, "unit_s%d_c%d_%dx%d", S, C, to.H, to.W);
 #define PF_DETUNIT_CASE(CC, KK, SS, MAXR, NTHR, PERCU)                                                             \
     if (C == CC && K1 == KK && S == SS) {                                                                          \
         det_pick_tile(h->num_cus, to.H, to.W, SS, MAXR, B, PERCU, &a.TH, &a.TW);                                               \
@@ -46,10 +43,10 @@ static int launch_detc3(pf_handle* h, const Program& p, const PfDetc3Op& o, int 
     const PfTensorRec& ta = p.tens[o.srcA_t];
     DetC3Args a{};
     a.srcA = (const float*)p.tensor_ptr(o.srcA_t); a.ldA = ta.ld; a.CA = ta.C;
-    if (o.srcB_t >= 0) { a.srcB = (const float*)p.tensor_ptr(o.srcB_t); a.ldB = p.tens[o.srcB_t].ld; }
-    if (o.out_t >= 0) { a.out = (float*)p.tensor_ptr(o.out_t); a.outLd = p.tens[o.out_t].ld; }
-    if (o.out2_t >= 0) { a.out2 = (float*)p.tensor_ptr(o.out2_t); a.out2Ld = p.tens[o.out2_t].ld; }
-    if (o.rows_buf >= 0) a.rows = (float*)p.buf_ptr(o.rows_buf);
+    a.srcB = (const float*)p.opt_tensor(o.srcB_t); a.ldB = p.opt_ld(o.srcB_t);
+    a.out = (float*)p.opt_tensor(o.out_t); a.outLd = p.opt_ld(o.out_t);
+    a.out2 = (float*)p.opt_tensor(o.out2_t); a.out2Ld = p.opt_ld(o.out2_t);
+    a.rows = (float*)p.opt_buf(o.rows_buf);
     a.wA = (const pf_half*)p.cptr(o.wA); a.bA = (const float*)p.cptr(o.bA);
     a.wB = (const pf_half*)p.cptr(o.wB); a.bB = (const float*)p.cptr(o.bB);
     a.wC = (const pf_half*)p.cptr(o.wC); a.bC = (const float*)p.cptr(o.bC);
@@ -66,10 +63,7 @@ static int launch_detc3(pf_handle* h, const Program& p, const PfDetc3Op& o, int 
     if (ta.C + cb != CIN || (ta.C % 8) || (o.srcB_t >= 0 && (p.tens[o.srcB_t].H != a.H || p.tens[o.srcB_t].W != a.W)) ||
         (tail == 1 && !a.out2) || (tail == 2 && (!a.rows || !a.anchors)))
         PF_FAIL(h, "detc3: inconsistent shapes");
-    char tagbuf[96];
-    tagbuf[0] = 0;
-    if (h->profiling) snprintf(tagbuf, sizeof(tagbuf), "c3_c%d_t%d_%dx%d", CIN, tail, a.H, a.W);
-    ProfScope ps(h, tagbuf);
+    ProfScope ps(h, "c3_c%d_t%d_%dx%d", CIN, tail, a.H, a.W);
 #define PF_DETC3_CASE(CC, TT, MAXR, NTHR)                                                                          \
     if (CIN == CC && tail == TT) {                                                                                 \
         det_pick_tile(h->num_cus, a.H, a.W, 1, MAXR, B, 1, &a.TH, &a.TW);                                                      \

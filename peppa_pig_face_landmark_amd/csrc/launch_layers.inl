@@ -53,10 +53,7 @@ static int launch_dw(pf_handle* h, const Program& p, const PfDwOp& o, int B) {
     a.B = B; a.inH = ti.H; a.inW = ti.W; a.C = ti.C; a.inLd = ti.ld;
     a.outH = to.H; a.outW = to.W; a.outLd = to.ld;
     a.K = o.K; a.stride = o.stride; a.pad = o.pad; a.dil = o.dil; a.act = o.act;
-    char tagbuf[64];
-    tagbuf[0] = 0;
-    if (h->profiling) snprintf(tagbuf, sizeof(tagbuf), "dw%dx%ds%dd%d_c%d_%dx%d", a.K, a.K, a.stride, a.dil, a.C, a.outH, a.outW);
-    ProfScope ps(h, tagbuf);
+    ProfScope ps(h, "dw%dx%ds%dd%d_c%d_%dx%d", a.K, a.K, a.stride, a.dil, a.C, a.outH, a.outW);
     auto tgrid = [&](int tx) {
         const long long n = (long long)B * to.H * ((to.W + tx - 1) / tx) * (ti.C / VE);
         return dim3((unsigned)((n + 255) / 256));

@@ -16,10 +16,7 @@ static int launch_chain(pf_handle* h, const Program& p, const PfChainOp& o, int 
     }
     a.range_slot = range_slot;
     a.dbg = h->dbg;
-    char tagbuf[96];
-    tagbuf[0] = 0;
-    if (h->profiling) snprintf(tagbuf, sizeof(tagbuf), "chain%d_c%d_%dx%d", a.n_convs, C, ti.H, ti.W);
-    ProfScope ps(h, tagbuf);
+    ProfScope ps(h, "chain%d_c%d_%dx%d", a.n_convs, C, ti.H, ti.W);
     // 16 / 12 waves per workgroup and a 3 / 4-stage weight ring: measured against 8 waves and against two stages
     // (profiles/r02_run14_teacher_*): 1.30 vs 1.38 / 1.39 ms and 0.68 vs 0.75 / 0.83 ms per 64 faces
     if (C == 72 && ti.H == 16) PF_LAUNCH((basic_chain_kernel<72, 16, 8, 2, 3, 3>), dim3(B), dim3(1024), h->stream, a);
@@ -42,10 +39,7 @@ static int launch_block(pf_handle* h, const Program& p, const PfBlockOp& o, int 
     }
     a.range_slot = range_slot;
     a.dbg = h->dbg;
-    char tagbuf[96];
-    tagbuf[0] = 0;
-    if (h->profiling) snprintf(tagbuf, sizeof(tagbuf), "block_c%d_%dx%d", C, ti.H, ti.W);
-    ProfScope ps(h, tagbuf);
+    ProfScope ps(h, "block_c%d_%dx%d", C, ti.H, ti.W);
     if (C == 18 && ti.W == 64) PF_LAUNCH((basic_block_kernel<18, 64, 4, 7, 1>), dim3(B * (ti.H / 4)), dim3(512), h->stream, a);
     else if (C == 36 && ti.W == 32) PF_LAUNCH((basic_block_kernel<36, 32, 8, 1, 2>), dim3(B * (ti.H / 8)), dim3(512), h->stream, a);
     else if (C == 18 && ti.W == 16) PF_LAUNCH((basic_block_kernel<18, 16, 8, 7, 1>), dim3(B * (ti.H / 8)), dim3(512), h->stream, a);
@@ -82,14 +76,11 @@ static int launch_hrb(pf_handle* h, const Program& p, const PfHrbOp& o, int B, u
     a.tiles_x = pf_div_up(ti.W, a.TW);
     a.tpf = a.tiles_x * pf_div_up(ti.H, a.TR);
     a.range_slot = range_slot;
-    if (host_dbg(h) & 4096) {
-        if (!h->d_dbg) { PF_HIP(h, hipMalloc((void**)&h->d_dbg, 64 * 16 * sizeof(unsigned long long))); PF_HIP(h, hipMemset(h->d_dbg, 0, 64 * 16 * sizeof(unsigned long long))); }
-        a.prof = h->d_dbg + 144 + (CIN == 64 ? 0 : 4);
+    if (host_dbg(h) & PF_ACC_DET_CYCLES) {      // per-phase cycle accounting (ablation build; printed at pf_destroy)
+        if (ensure_cycle_counters(h)) return 1;
+        a.prof = h->d_dbg + PF_CYC_HRB.at(CIN == 64 ? 0 : 1);
     }
-    char tagbuf[96];
-    tagbuf[0] = 0;
-    if (h->profiling) snprintf(tagbuf, sizeof(tagbuf), "bottleneck_c%d_%dx%d", CIN, ti.H, ti.W);
-    ProfScope ps(h, tagbuf);
+    ProfScope ps(h, "bottleneck_c%d_%dx%d", CIN, ti.H, ti.W);
     if (CIN == 64) PF_LAUNCH((hr_bottleneck_kernel<64, true, 272, 128, 1>), dim3(a.tpf * B), dim3(1024), h->stream, a);
     else if (CIN == 256) PF_LAUNCH((hr_bottleneck_kernel<256, false, 272, 128, 1>), dim3(a.tpf * B), dim3(1024), h->stream, a);
     else PF_FAIL(h, "hrb: no kernel for %d input channels", CIN);

@@ -1,20 +1,14 @@
 // Shared device-side helpers: activation-type traits, 16-byte vectors, activation functions.
 //
 // Activations are NHWC.  The engine is instantiated for two element types:
-//   pf_half (f16 storage, f32 accumulate, v_mfma_f32_16x16x32_f16)  -- the production path
-//   float   (f32 storage, v_mfma_f32_16x16x4_f32)                   -- exact verification path
+//   pf_half (f16 storage, f32 accumulate, v_mfma_f32_16x16x32_f16)
+//   float   (f32 storage): exact f32 programs (v_mfma_f32_16x16x4_f32, the verification path) and split-precision f32s programs
+//           (every operand as f16 hi + lo, products on v_mfma_f32_16x16x32_f16) -- f32s is the production path
 // Every kernel moves activations as 16-byte vectors: 8 x f16 or 4 x f32.
 #pragma once
 #include <pf_intrinsics.h>  // resolved through -I (csrc/ for the product build)
 
-// Timing ablations (wave-uniform bit masks tested inside the GEMM kernels; results are WRONG when set) exist only in the
-// ablation build -- `python -m peppa_pig_face_landmark_amd.build --ablate` compiles the same sources with -DPF_ABLATE=1 into
-// libpeppa_hip_ablate.so for tools/ab_env.py.  In the production library pf_dbg() is the constant 0: every ablation branch
-// folds away, and no environment variable can make a kernel skip work or switch the range guard off.
-#ifndef PF_ABLATE
-#define PF_ABLATE 0
-#endif
-template <typename Args> __device__ __forceinline__ int pf_dbg(const Args& a) { return PF_ABLATE ? a.dbg : 0; }
+#include "pf_ablate.h"     // PF_ABLATE, pf_dbg() and the named PEPPA_DBG bits of the ablation build
 
 // ---- range guard of the split-precision (f32s) kernels, always on ---------------------------------------------------------------
 // Every kernel that writes f32 values as f16 hi + lo keeps a running maximum of |v| over EVERYTHING it splits, as raw bits

@@ -1,7 +1,9 @@
 """A/B timing of kernel variants selected by environment variables (run on the GPU box).
 usage: python tools/ab_env.py "<tag substring,tag substring,...>" "NAME=VAL NAME2=VAL" "NAME=VAL" ...
 Each remaining argument is one variant: a space-separated list of environment assignments ("-" = none).
-Prints whole-pipeline faces/s and the per-lane-step ms of every kernel tag containing one of the substrings."""
+Prints whole-pipeline faces/s and the per-lane-step ms of every kernel tag containing one of the substrings.
+PEPPA_DBG is a bit mask; peppa_pig_face_landmark_amd/csrc/pf_ablate.h opens with the table of its bits -- which kernels and launchers
+read each value, which values mean different things in different kernels, and which leave the results right."""
 import json, os, subprocess, sys
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 from peppa_pig_face_landmark_amd import build as _b  # noqa: E402
@@ -25,7 +27,7 @@ for vi, spec in enumerate(sys.argv[2:]):
         sel = {n: round(v["ms_per_step"], 4) for n, v in k.items() if any(s in n for s in subs)}
         print("%-40s %8.0f faces/s  serial %.3f ms  %s" % (spec, d["value"], d["extra"]["lane_step_ms_serial"], sel), flush=True)
         for l in r.stderr.splitlines():
-            if l.startswith("[hero_pipe") or l.startswith("[sepup_pipe") or l.startswith("[det_"):     # cycle accounting of the ablation build (PEPPA_DBG & 64)
+            if l.startswith("[hero_pipe") or l.startswith("[sepup_pipe") or l.startswith("[det_"):     # cycle accounting of the ablation build (PF_ACC_CYCLES = 64, PF_ACC_DET_CYCLES = 4096)
                 print("    " + l, flush=True)
     except Exception as e:  # noqa: BLE001
         print(spec, "FAILED", e, r.stderr[-800:], flush=True)

@@ -77,6 +77,37 @@ int pf_landmark_forward(pf_handle* h, const void* input, int input_kind, int mem
  * call left no rows or when more rows are asked than it left. */
 int pf_face_attrs(pf_handle* h, int rows, float* out, int raw, int out_mem);
 
+/* Aligned face chips: the similarity warp of a face onto the public ArcFace five-point template, the normalised image that
+ * recognition / liveness / attribute networks take, cut on the device from the frame and the 98 landmarks.  Arithmetic (the
+ * specification, restated in numpy by tests/align_ref.py): five points in float64 -- the means of landmarks
+ * 60..67 and 68..75 (the eye contours; not the pupils 96 / 97, which follow the gaze), 54 (nose tip), 76 and 82 (mouth corners) --
+ * fitted to the template scaled by chip_size / 112 as a least-squares similarity without reflection, in closed form:
+ * M = [[a, -b, tx], [b, a, ty]] maps frame to chip.  A slot is valid iff the fit is finite and a^2 + b^2 lies in [2^-12, 2^12].
+ * Every chip pixel is the bilinear sample at M^-1 (x, y), the coordinate rounded to 1/1024 pixel and the blend done in integers
+ * ((sum of tap * weight + 2^19) >> 20), taps outside the frame reading 0; channel order untouched.  No float64 operation is
+ * contracted into an fma, so the bytes are the same on every machine.  LIMIT: there is no anti-alias pre-filter -- a face much
+ * larger than the chip aliases exactly as cv2.warpAffine(INTER_LINEAR) would.  chip_size: a multiple of 16 in [32, 256].
+ *
+ * pf_align_faces is the stage-level entry (like pf_crop_faces): frames [F][H][W][3] packed (mem = PF_MEM_HOST, PF_MEM_DEVICE or
+ * PF_MEM_RESIDENT -- then n_frames must be 1 and frames may be NULL); kps [F][top_k][98][2] float32 (kps_f64 = 0) or float64,
+ * in host or device memory (kps_mem); counts [F] in the same memory as kps, slot k of frame f being live iff k < counts[f]
+ * (NULL: all top_k slots).  Outputs in host or device memory (out_mem): chips [F][top_k][S][S][3], mats [F][top_k][2][3]
+ * float64, valid [F][top_k] (0 for dead or degenerate slots, whose chip and matrix rows are left untouched, like the kps of
+ * pf_landmarks); mats and valid may be NULL.  Device outputs are enqueued on the handle's stream, host outputs are copied and
+ * synchronised. */
+int pf_align_faces(pf_handle* h, const uint8_t* frames, int mem, int n_frames, int height, int width,
+                   const void* kps, int kps_f64, int kps_mem, const int* counts, int top_k, int chip_size,
+                   uint8_t* chips, double* mats, int* valid, int out_mem);
+/* The chips of the faces of the handle's last pipeline call, cut from the frame(s) and landmarks that call left on the device;
+ * row semantics exactly those of pf_face_attrs: after pf_landmarks* box order (rows whose valid flag is 0 are dead), after
+ * pf_run_frames* [F][top_k] with the device counts, after pf_track_frame* the n_out tracked faces with their smoothed float64
+ * landmarks, after pf_track_streams [n][top_k] with out_lm / the counts, the frames read from the stream slots.  FRAME LIFETIME:
+ * frames the call was given with mem = PF_MEM_DEVICE are read again here and must still be alive and unchanged; frames given from
+ * host memory are read from the handle's staging copy, which the next call that stages a frame overwrites (that call then leaves
+ * no rows).  Fails with a message after pf_landmark_forward (no frame), when the last call left no rows and when more rows are
+ * asked than it left. */
+int pf_face_chips(pf_handle* h, int rows, int chip_size, uint8_t* chips, double* mats, int* valid, int out_mem);
+
 /* Detector forward == session.run of yolov5n-0.5.onnx (face_detector.py:29-31):
  * input float32 NCHW [1][3][384][640] RGB/255 or uint8 NHWC letterboxed RGB;
  * output [rows][16] decoded rows (cx,cy,w,h,obj,10 landmark coords,cls), rows = 15120 at 384x640. */
@@ -291,6 +322,9 @@ int pf_batch_run_frames(pf_batch* b, const uint8_t* frames, int mem, int n_frame
 /* pf_face_attrs of the lanes, gathered: the [n_frames][top_k][7] attribute rows of the last pf_batch_run_frames (front mode
  * on or off), laid out like its kps.  Device output is enqueued on the lanes' streams. */
 int pf_batch_face_attrs(pf_batch* b, int rows, float* out, int raw, int out_mem);
+/* pf_face_chips of the lanes, gathered the same way: chips [n_frames][top_k][S][S][3] (mats, valid alike) of the last
+ * pf_batch_run_frames, front mode on or off.  Device-resident frames of that call must still be alive. */
+int pf_batch_face_chips(pf_batch* b, int rows, int chip_size, uint8_t* chips, double* mats, int* valid, int out_mem);
 
 /* Engine options.  PF_OPT_HIP_GRAPH = 1: pf_run_frames* calls whose buffers all live on the device are captured
  * into a hipGraph per distinct (pointers, shapes, thresholds) and replayed (launch-latency bound small batches). */

@@ -51,6 +51,12 @@ def _declare(lib):
         lib.pf_face_attrs.restype = i
         lib.pf_batch_face_attrs.argtypes = [vp, i, vp, i, i]
         lib.pf_batch_face_attrs.restype = i
+    if hasattr(lib, "pf_align_faces"):     # likewise
+        lib.pf_align_faces.argtypes = [vp, vp, i, i, i, i, vp, i, i, vp, i, i, vp, vp, vp, i]
+        lib.pf_face_chips.argtypes = [vp, i, i, vp, vp, vp, i]
+        lib.pf_batch_face_chips.argtypes = [vp, i, i, vp, vp, vp, i]
+        for name in ("pf_align_faces", "pf_face_chips", "pf_batch_face_chips"):
+            getattr(lib, name).restype = i
     lib.pf_detect.argtypes = [vp, vp, i, i, i, i, f, f, fp, i, ip]
     lib.pf_landmarks.argtypes = [vp, vp, i, i, i, i, fp, i, fp, fp, ip]
     lib.pf_landmarks_f64.argtypes = [vp, vp, i, i, i, i, C.POINTER(C.c_double), i, fp, fp, ip]
@@ -296,6 +302,57 @@ class Engine:
     def face_attrs_device(self, rows: int, d_out: int, raw: bool = False):
         """Same into device memory, enqueued on the handle's stream."""
         self._check(self.lib.pf_face_attrs(self.h, int(rows), _ptr(d_out), 1 if raw else 0, PF_MEM_DEVICE), "pf_face_attrs")
+
+    # ---- aligned face chips (include/peppa_hip.h pf_align_faces / pf_face_chips) -------------------------------------------------
+    def align_faces(self, frames, kps: np.ndarray, counts: Optional[np.ndarray] = None, chip_size: int = 112, out=None):
+        """Similarity-warped face chips.  frames: uint8 [F,H,W,3] (or [H,W,3]), ``None`` for the resident frame of set_frame(), or
+        ``(device pointer, F, H, W)``; kps: float32 or float64 [F,top_k,98,2] (or [top_k,98,2] for one frame); counts: [F] live slots
+        per frame (None: all).  Returns (chips uint8 [F,top_k,S,S,3], mats float64 [F,top_k,2,3] frame -> chip, valid bool [F,top_k]);
+        chips and matrices of invalid slots are left as they were (zero, or what ``out = (chips, mats)`` held)."""
+        k = np.asarray(kps)
+        k = np.ascontiguousarray(k, np.float64 if k.dtype == np.float64 else np.float32)
+        if k.ndim == 3:
+            k = k[None]
+        if k.ndim != 4 or k.shape[2:] != (98, 2):
+            raise ValueError("kps must be [F,top_k,98,2]")
+        F, K = k.shape[:2]
+        if frames is None:
+            shp = getattr(self, "_resident_shape", None)
+            if shp is None:
+                raise PeppaHipError("no resident frame: call set_frame() first")
+            fptr, mem, nf, H, W, keep = None, PF_MEM_RESIDENT, F, shp[0], shp[1], None
+        elif isinstance(frames, tuple):
+            fptr, mem, (nf, H, W), keep = C.c_void_p(int(frames[0])), PF_MEM_DEVICE, (int(v) for v in frames[1:]), None
+        else:
+            keep = np.ascontiguousarray(frames)
+            if keep.ndim == 3:
+                keep = keep[None]
+            if keep.dtype != np.uint8 or keep.ndim != 4 or keep.shape[3] != 3:
+                raise ValueError("frames must be uint8 [F,H,W,3]")
+            fptr, mem, (nf, H, W) = _ptr(keep), PF_MEM_HOST, keep.shape[:3]
+        if nf != F:
+            raise ValueError("%d frames, landmarks of %d" % (nf, F))
+        c = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
+        S = int(chip_size)
+        chips, mats = out if out is not None else (np.zeros((F, K, max(S, 0), max(S, 0), 3), np.uint8), np.zeros((F, K, 2, 3), np.float64))
+        valid = np.zeros((F, K), np.int32)
+        self._check(self.lib.pf_align_faces(self.h, fptr, mem, F, H, W, _ptr(k), 1 if k.dtype == np.float64 else 0, PF_MEM_HOST,
+                                            _ptr(c), K, S, _ptr(chips), _ptr(mats), _ptr(valid), PF_MEM_HOST), "pf_align_faces")
+        return chips, mats, valid.astype(bool)
+
+    def face_chips(self, rows: int, chip_size: int = 112, out=None):
+        """Chips of the faces of the handle's last pf_landmarks / pf_run_frames / pf_track_frame / pf_track_streams call, in that
+        call's row order (include/peppa_hip.h pf_face_chips): (chips uint8 [rows,S,S,3], mats float64 [rows,2,3], valid bool [rows])."""
+        S, rows = int(chip_size), int(rows)
+        chips, mats = out if out is not None else (np.zeros((rows, max(S, 0), max(S, 0), 3), np.uint8), np.zeros((rows, 2, 3), np.float64))
+        valid = np.zeros((rows,), np.int32)
+        self._check(self.lib.pf_face_chips(self.h, rows, S, _ptr(chips), _ptr(mats), _ptr(valid), PF_MEM_HOST), "pf_face_chips")
+        return chips, mats, valid.astype(bool)
+
+    def face_chips_device(self, rows: int, chip_size: int, d_chips: int, d_mats: int = 0, d_valid: int = 0):
+        """Same into device memory, enqueued on the handle's stream."""
+        self._check(self.lib.pf_face_chips(self.h, int(rows), int(chip_size), _ptr(d_chips), _ptr(d_mats) if d_mats else None,
+                                           _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE), "pf_face_chips")
 
     def landmark_forward_device(self, d_input: int, kind: int, batch: int, d_loc: int = 0, d_score: int = 0):
         """Same on device pointers (bench): nothing crosses PCIe."""
@@ -772,6 +829,21 @@ class BatchEngine:
     def face_attrs_device(self, rows: int, d_out: int, raw: bool = False):
         """Same into device memory, enqueued on the lanes' streams."""
         self._check(self.lib.pf_batch_face_attrs(self.b, int(rows), _ptr(d_out), 1 if raw else 0, PF_MEM_DEVICE), "pf_batch_face_attrs")
+
+    def face_chips(self, rows: int, chip_size: int = 112):
+        """Chips of the last run_frames* call, laid out like its kps ([F * top_k]; include/peppa_hip.h pf_batch_face_chips):
+        (chips uint8 [rows,S,S,3], mats float64 [rows,2,3], valid bool [rows])."""
+        S, rows = int(chip_size), int(rows)
+        chips = np.zeros((rows, max(S, 0), max(S, 0), 3), np.uint8)
+        mats = np.zeros((rows, 2, 3), np.float64)
+        valid = np.zeros((rows,), np.int32)
+        self._check(self.lib.pf_batch_face_chips(self.b, rows, S, _ptr(chips), _ptr(mats), _ptr(valid), PF_MEM_HOST), "pf_batch_face_chips")
+        return chips, mats, valid.astype(bool)
+
+    def face_chips_device(self, rows: int, chip_size: int, d_chips: int, d_mats: int = 0, d_valid: int = 0):
+        """Same into device memory, enqueued on the lanes' streams."""
+        self._check(self.lib.pf_batch_face_chips(self.b, int(rows), int(chip_size), _ptr(d_chips), _ptr(d_mats) if d_mats else None,
+                                                 _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE), "pf_batch_face_chips")
 
     def close(self):
         self._host.close()

@@ -27,13 +27,17 @@ from .hip_model_base import _RANGE_ERR
 class FrameBatchRunner:
     def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, lanes: int = 3, frames_per_lane: int = 32,
                  device: Optional[int] = None, library: Optional[str] = None, graph: bool = True, top_k: Optional[int] = None,
-                 face_attributes: Optional[bool] = None):
-        """``face_attributes`` (default: ``Engine.face_attributes`` of Skps.yml): every result dict also gets ``"pose"`` and
+                 face_attributes: Optional[bool] = None, face_chips: Optional[int] = None):
+        """``face_chips`` (default: ``Engine.face_chips`` of Skps.yml, 0 = off): a chip size adds ``"chip"`` and ``"chip_matrix"`` to
+        every result dict as in ``FaceAna``.
+
+        ``face_attributes`` (default: ``Engine.face_attributes`` of Skps.yml): every result dict also gets ``"pose"`` and
         ``"attrs"`` as in ``FaceAna``."""
         cfg = cfg or get_cfg()
         sk = cfg["Skps"]
         eng_cfg = sk.get("Engine", {})
         self.face_attributes = bool(eng_cfg.get("face_attributes", False)) if face_attributes is None else bool(face_attributes)
+        self.face_chips = int(eng_cfg.get("face_chips", 0) or 0) if face_chips is None else int(face_chips or 0)
         self.device = int(eng_cfg.get("device", 0)) if device is None else int(device)
         self.dtype = eng_cfg.get("dtype", "f32s")
         root = pathlib.Path(__file__).resolve().parents[2]
@@ -51,6 +55,7 @@ class FrameBatchRunner:
         self.track_iou_thres = float(sk["Trace"]["iou_thres"])
         self._box_filter = EmaFilter(float(sk["Trace"]["smooth_box"]))
         self.lanes, self.frames_per_lane = int(lanes), int(frames_per_lane)
+        self._planted_rows = None    # test instrument: callable(frames [F,H,W,3]) -> decoded detector rows [F,R,16] for run()
         self.engine = _native.BatchEngine(self.device, self.lanes, library)
         self.engine.set_option(_native.PF_OPT_HIP_GRAPH, 1 if graph else 0)
         self._load(_native.PF_NET_DETECTOR, self.dtype)
@@ -96,9 +101,16 @@ class FrameBatchRunner:
             raise ValueError("%d frames exceed lanes * frames_per_lane = %d" % (frames.shape[0], self.max_frames))
         return self._guarded(self.engine.run_frames, frames, self.score_thrs, self.iou_thrs, self.min_face, self.top_k, planted_rows)
 
-    def _run_with_attrs(self, frames, planted_rows=None):
+    def _run_with_extras(self, frames, planted_rows=None):
+        """run_frames + the attribute rows and / or chips of the same call ([F][top_k] rows, like kps)."""
         r = self.engine.run_frames(frames, self.score_thrs, self.iou_thrs, self.min_face, self.top_k, planted_rows)
-        return r + (self.engine.face_attrs(r[0].shape[0] * self.top_k).reshape(r[0].shape[0], self.top_k, 7),)
+        F, K = r[0].shape[0], self.top_k
+        attrs = self.engine.face_attrs(F * K).reshape(F, K, 7) if self.face_attributes else None
+        chips = None
+        if self.face_chips:
+            c, m, v = self.engine.face_chips(F * K, self.face_chips)
+            chips = (c.reshape((F, K) + c.shape[1:]), m.reshape(F, K, 2, 3), v.reshape(F, K))
+        return r + (attrs, chips)
 
     def _returned_boxes(self, det_boxes: np.ndarray, kps: np.ndarray) -> np.ndarray:
         """The 'box' a fresh ``FaceAna.run`` hands back (facer.py:81-84): not the detector's box but the hull of the face's
@@ -121,20 +133,27 @@ class FrameBatchRunner:
         out: List[List[Dict[str, np.ndarray]]] = []
         for s in range(0, frames.shape[0], self.max_frames):
             chunk = frames[s:s + self.max_frames]
-            if self.face_attributes:
+            attrs = chips = None
+            planted = self._planted_rows(chunk) if self._planted_rows is not None else None
+            if self.face_attributes or self.face_chips:
                 if chunk.ndim != 4 or chunk.shape[-1] != 3 or chunk.dtype != np.uint8:
                     raise ValueError("frames must be uint8 [F,H,W,3]")
-                counts, boxes, kps, scores, attrs = self._guarded(self._run_with_attrs, chunk)
+                counts, boxes, kps, scores, attrs, chips = self._guarded(self._run_with_extras, chunk, planted)
             else:
-                counts, boxes, kps, scores = self.run_arrays(chunk)
+                counts, boxes, kps, scores = self.run_arrays(chunk, planted)
             for f in range(counts.shape[0]):
                 n = int(counts[f])
                 ret = self._returned_boxes(boxes[f, :n], kps[f, :n]) if n else np.zeros((0, 4), np.float32)
                 res = [{"box": ret[i], "kps": kps[f, i], "scores": scores[f, i], "det_box": boxes[f, i]} for i in range(n)]
-                if self.face_attributes:        # per-frame network output, not smoothed
+                if attrs is not None:           # per-frame network output, not smoothed
                     for i, d in enumerate(res):
                         d["pose"] = attrs[f, i, :3].copy()
                         d["attrs"] = attrs[f, i, 3:7].copy()
+                if chips is not None:           # cut with the landmarks the result carries; a degenerate fit gets neither key
+                    for i, d in enumerate(res):
+                        if chips[2][f, i]:
+                            d["chip"] = chips[0][f, i].copy()
+                            d["chip_matrix"] = chips[1][f, i].copy()
                 out.append(res)
         return out
 

@@ -76,8 +76,14 @@ def _box_iou(a, b) -> float:
 
 class FaceAna:
     def __init__(self, verbose: bool = False, cfg: Optional[dict] = None, weights: Optional[dict] = None,
-                 device: Optional[int] = None, library: Optional[str] = None, face_attributes: Optional[bool] = None):
-        """``face_attributes`` (default: ``Engine.face_attributes`` of Skps.yml, false): every result dict also gets ``"pose"``
+                 device: Optional[int] = None, library: Optional[str] = None, face_attributes: Optional[bool] = None,
+                 face_chips: Optional[int] = None):
+        """``face_chips`` (default: ``Engine.face_chips`` of Skps.yml, 0 = off): a chip size S (a multiple of 16 in [32, 256], e.g.
+        112) makes every result dict also carry ``"chip"`` (uint8 [S,S,3], BGR: the face warped onto the ArcFace five-point template
+        on the GPU, cut with the landmarks the result carries) and ``"chip_matrix"`` (float64 [2,3], frame -> chip); a face whose
+        fit is degenerate gets neither key.  No anti-alias pre-filter is applied when the face is larger than the chip.
+
+        ``face_attributes`` (default: ``Engine.face_attributes`` of Skps.yml, false): every result dict also gets ``"pose"``
         (float32 [3], head pose in degrees about x, y, z -- the per-frame network output, not smoothed) and ``"attrs"`` (float32 [4],
         P(eye of points 60-67 closed), P(eye of points 68-75 closed), P(mouth closed), P(mouth wide open)) from the landmark network's
         fc head, in both tracking modes.  Needs weights with ``fc.weight`` / ``fc.bias`` (a .pth checkpoint or an .npz made from one,
@@ -99,6 +105,7 @@ class FaceAna:
         # walking the boxes through numpy between the two networks on every frame
         self.device_tracking = bool(eng_cfg.get("device_tracking", False))
         self.face_attributes = bool(eng_cfg.get("face_attributes", False)) if face_attributes is None else bool(face_attributes)
+        self.face_chips = int(eng_cfg.get("face_chips", 0) or 0) if face_chips is None else int(face_chips or 0)
         self._planted_rows = None    # test instrument: callable returning decoded detector rows that replace the detector's own
         self._det_cfg = sk["Detect"]
         self.top_k = sk["Detect"]["topk"]
@@ -125,11 +132,10 @@ class FaceAna:
         # landmark stage; the frame-difference gate (facer.py:98-118) is evaluated on the GPU against the
         # previous resident frame (exact integer sum, same decision as the numpy code in diff_frames()).
         if self.device_tracking:
-            fn = self.engine.track_frame
-            if self.face_attributes:
-                def fn(*args):       # the attribute rows of the tracked faces, compacted like kps (pf_face_attrs after pf_track_frame)
-                    r = self.engine.track_frame(*args)
-                    return r + (self.engine.face_attrs(len(r[0])),)
+            def fn(*args):       # the attribute rows / chips of the tracked faces, compacted like kps (pf_face_attrs / pf_face_chips after pf_track_frame)
+                r = self.engine.track_frame(*args)
+                return r + (self.engine.face_attrs(len(r[0])) if self.face_attributes else None,
+                            self.engine.face_chips(len(r[0]), self.face_chips) if self.face_chips and len(r[0]) else None)
             out = run_guarded(
                 [self.face_detector.model, self.face_landmark.model], fn, image, float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]),
                 float(self.min_face), int(self.top_k), float(self.iou_thres), float(self.alpha), float(self.diff_thres),
@@ -137,7 +143,7 @@ class FaceAna:
             boxes, kps, scores = out[:3]
             self.previous_image = image
             self.track_box = boxes
-            return self.to_dict(boxes, kps, scores, out[4] if self.face_attributes else None)
+            return self.to_dict(boxes, kps, scores, out[4], out[5])
         diff = self.engine.set_frame(image)
         self.previous_image = image
         if diff is None or self.track_box is None or diff > self.diff_thres:
@@ -156,7 +162,11 @@ class FaceAna:
         landmarks = self.trace.calculate(image, landmarks)
         hulls = [[np.min(l[:, 0]), np.min(l[:, 1]), np.max(l[:, 0]), np.max(l[:, 1])] for l in landmarks]
         self.track_box = self.judge_boxs(boxes_return, np.array(hulls))
-        return self.to_dict(self.track_box, landmarks, states, attrs)
+        chips = None
+        if self.face_chips and len(landmarks):      # cut with the smoothed landmarks the result carries, from the resident frame
+            c, m, v = self.engine.align_faces(None, np.asarray(landmarks)[None], chip_size=self.face_chips)
+            chips = (c[0], m[0], v[0])
+        return self.to_dict(self.track_box, landmarks, states, attrs, chips)
 
     def imread(self, path_or_bytes, want_host: bool = True):
         """``cv2.imread(path)`` of the reference's demo (demo.py:76) for baseline JPEG files: the Huffman stream is decoded on
@@ -182,12 +192,19 @@ class FaceAna:
                 logger.warning("imread: %s", e)
             return frame
 
-    def to_dict(self, bboxes, kps, states, attrs=None):
+    @staticmethod
+    def to_dict(bboxes, kps, states, attrs=None, chips=None):
+        """``chips``: (chips [n,S,S,3], matrices [n,2,3], valid [n]) of the same rows (Engine.face_chips / align_faces)."""
         out = [{"box": bboxes[i], "kps": kps[i], "scores": states[i]} for i in range(len(bboxes))]
         if attrs is not None:
             for i, d in enumerate(out):
                 d["pose"] = np.asarray(attrs[i, :3], np.float32).copy()
                 d["attrs"] = np.asarray(attrs[i, 3:7], np.float32).copy()
+        if chips is not None:
+            for i, d in enumerate(out):
+                if chips[2][i]:
+                    d["chip"] = chips[0][i].copy()
+                    d["chip_matrix"] = chips[1][i].copy()
         return out
 
     def diff_frames(self, previous_frame, image) -> bool:

@@ -16,15 +16,18 @@ import numpy as np
 
 from ... import _native
 from ...logger.logger import logger
-from .facer import _load_weights, get_cfg
+from .facer import FaceAna, _load_weights, get_cfg
 from .hip_model_base import HIPEngine, run_guarded
 
 
 class StreamTracker:
     def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, max_streams: int = 8,
                  device: Optional[int] = None, library: Optional[str] = None, verbose: bool = False,
-                 face_attributes: Optional[bool] = None):
-        """``face_attributes`` (default: ``Engine.face_attributes`` of Skps.yml): every result dict also gets ``"pose"`` and
+                 face_attributes: Optional[bool] = None, face_chips: Optional[int] = None):
+        """``face_chips`` (default: ``Engine.face_chips`` of Skps.yml, 0 = off): a chip size adds ``"chip"`` and ``"chip_matrix"`` to
+        every result dict as in ``FaceAna``.
+
+        ``face_attributes`` (default: ``Engine.face_attributes`` of Skps.yml): every result dict also gets ``"pose"`` and
         ``"attrs"`` as in ``FaceAna`` (per-frame network output, not smoothed)."""
         if verbose:
             logger.setLevel(logging.DEBUG)
@@ -42,6 +45,7 @@ class StreamTracker:
         kps_w = weights.get("keypoints") or _load_weights(root, sk["Keypoints"]["model_path"], "teacher" if kps_arch == "teacher" else "keypoints")
 
         self.face_attributes = bool(eng_cfg.get("face_attributes", False)) if face_attributes is None else bool(face_attributes)
+        self.face_chips = int(eng_cfg.get("face_chips", 0) or 0) if face_chips is None else int(face_chips or 0)
         self.max_streams = int(max_streams)
         self.top_k = int(sk["Detect"]["topk"])
         self._det_cfg = sk["Detect"]
@@ -72,24 +76,22 @@ class StreamTracker:
 
         def call(*args):
             r = self.engine.track_streams(*args)
-            if not self.face_attributes:
-                return r, None
-            attrs = self.engine.face_attrs(len(r) * K)           # [n][top_k] rows, compacted like kps
-            return r, [attrs[i * K:i * K + len(b)] for i, (b, _, _, _) in enumerate(r)]
-        res, attrs = run_guarded([self.detector, self.landmark], call, ids, batch,
+            attrs = chips = None
+            if self.face_attributes:
+                a = self.engine.face_attrs(len(r) * K)           # [n][top_k] rows, compacted like kps
+                attrs = [a[i * K:i * K + len(b)] for i, (b, _, _, _) in enumerate(r)]
+            if self.face_chips:
+                c = self.engine.face_chips(len(r) * K, self.face_chips)      # the same rows
+                chips = [tuple(x[i * K:i * K + len(b)] for x in c) for i, (b, _, _, _) in enumerate(r)]
+            return r, attrs, chips
+        res, attrs, chips = run_guarded([self.detector, self.landmark], call, ids, batch,
                                  float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]), float(self.min_face),
                                  float(self.iou_thres), float(self.alpha), float(self.diff_thres), planted)
         self.last_detector_ran = {s: ran for s, (_, _, _, ran) in zip(ids, res)}   # did the gate run the detector
-        return {s: self.to_dict(b, k, sc, attrs[i] if attrs is not None else None) for i, (s, (b, k, sc, _)) in enumerate(zip(ids, res))}
+        return {s: self.to_dict(b, k, sc, attrs[i] if attrs is not None else None, chips[i] if chips is not None else None)
+                for i, (s, (b, k, sc, _)) in enumerate(zip(ids, res))}
 
-    @staticmethod
-    def to_dict(bboxes, kps, states, attrs=None):
-        out = [{"box": bboxes[i], "kps": kps[i], "scores": states[i]} for i in range(len(bboxes))]
-        if attrs is not None:
-            for i, d in enumerate(out):
-                d["pose"] = np.asarray(attrs[i, :3], np.float32).copy()
-                d["attrs"] = np.asarray(attrs[i, 3:7], np.float32).copy()
-        return out
+    to_dict = staticmethod(FaceAna.to_dict)
 
     def reset(self, stream_id: Optional[int] = None):
         """FaceAna.reset() of one stream, or of every stream (None)."""

@@ -38,6 +38,7 @@ struct pf_batch {
     bool ev_lane_live[2] = {false, false};
     // the last successful pf_batch_run_frames (pf_batch_face_attrs): frames and top_k; lane i holds the records of its slice
     int attr_frames = 0, attr_top_k = 0;
+    const int* last_sel_count = nullptr;     // front mode: the counts of that call (pf_batch_face_chips)
 };
 
 #define PF_BFAIL(b, ...)                                  \
@@ -220,6 +221,7 @@ static int batch_run_front(pf_batch* b, const uint8_t* frames, int n_frames, int
         }
     }
     b->ev_lane_live[par] = true;
+    b->last_sel_count = sel_count;
     return 0;
 }
 
@@ -255,7 +257,7 @@ int pf_batch_run_frames(pf_batch* b, const uint8_t* frames, int mem, int n_frame
     // every lane's share is checked BEFORE anything is enqueued: a lane that refuses its slice must not leave the lanes in front of
     // it writing into buffers the caller frees when the call fails
     b->attr_frames = 0;
-    for (pf_handle* h : b->lane) h->attr_kind = 0;
+    for (pf_handle* h : b->lane) { h->attr_kind = 0; h->align.kind = 0; }
     const Program& fdet = b->front->prog[PF_NET_DETECTOR];
     const bool front = b->front_mode && (mem & 0xff) == PF_MEM_DEVICE && (fdet.loaded ? n_frames <= fdet.max_batch : det_rows != nullptr);
     for (int i = 0; i < L; ++i) {
@@ -294,6 +296,9 @@ int pf_batch_run_frames(pf_batch* b, const uint8_t* frames, int mem, int n_frame
         const int nf = std::min(per, n_frames - i * per);
         if (nf <= 0) break;
         b->lane[i]->attr_kind = 1; b->lane[i]->attr_rows = nf * top_k;
+        if (front)       // pf_batch_face_chips (without the front engine pf_run_frames_planted has noted the lane's own slice)
+            chips_note_frames(b->lane[i], frames + (size_t)i * per * frame_bytes, frame_bytes, nf, height, width, width * 3, nf * top_k, top_k,
+                              b->lane[i]->pipe.d_kps, 0, b->last_sel_count + i * per);
     }
     b->attr_frames = n_frames; b->attr_top_k = top_k;
     if (out_mem != PF_MEM_HOST) return 0;
@@ -315,6 +320,25 @@ int pf_batch_face_attrs(pf_batch* b, int rows, float* out, int raw, int out_mem)
         const int r0 = i * per * K, nr = std::min(rows - r0, std::min(per, b->attr_frames - i * per) * K);
         if (nr <= 0) break;
         if (pf_face_attrs(b->lane[i], nr, out + (size_t)r0 * 7, raw, out_mem)) PF_BFAIL(b, "lane %d: %s", i, pf_last_error(b->lane[i]));
+    }
+    return 0;
+}
+
+/* pf_face_chips of the lanes, gathered like pf_batch_face_attrs: lane i cuts the chips of its slice of the last pf_batch_run_frames */
+int pf_batch_face_chips(pf_batch* b, int rows, int chip_size, uint8_t* chips, double* mats, int* valid, int out_mem) {
+    if (!b) return 1;
+    if (const char* why = align_check_size(chip_size)) PF_BFAIL(b, "pf_batch_face_chips: %s (got %d)", why, chip_size);
+    if (!align_out_mem_ok(out_mem)) PF_BFAIL(b, "pf_batch_face_chips: bad out_mem %d", out_mem);
+    if (b->attr_frames == 0) PF_BFAIL(b, "pf_batch_face_chips: no pf_batch_run_frames call has left face rows");
+    const int L = (int)b->lane.size(), K = b->attr_top_k;
+    if (!chips || rows < 0 || rows > b->attr_frames * K) PF_BFAIL(b, "pf_batch_face_chips: %d rows asked, the last call left %d", rows, b->attr_frames * K);
+    const int per = (b->attr_frames + L - 1) / L;
+    const size_t chip_bytes = (size_t)chip_size * chip_size * 3;
+    for (int i = 0; i < L; ++i) {
+        const int r0 = i * per * K, nr = std::min(rows - r0, std::min(per, b->attr_frames - i * per) * K);
+        if (nr <= 0) break;
+        if (pf_face_chips(b->lane[i], nr, chip_size, chips + (size_t)r0 * chip_bytes, mats ? mats + (size_t)r0 * 6 : nullptr,
+                          valid ? valid + r0 : nullptr, out_mem)) PF_BFAIL(b, "lane %d: %s", i, pf_last_error(b->lane[i]));
     }
     return 0;
 }

@@ -34,6 +34,7 @@
 #include "k_jpeg.h"
 #include "k_prepost.h"
 #include "k_track.h"
+#include "k_align.h"
 #include "pf_program.h"
 
 
@@ -124,6 +125,8 @@ struct pf_handle {
     std::vector<int> h_attr_valid;
     int* d_attr_valid = nullptr; size_t attr_valid_bytes = 0;
     float* d_track_attrs = nullptr; size_t track_attrs_bytes = 0;
+    // aligned face chips (align.inl): scratch, and where the last pipeline call left frames / landmarks / live flags (pf_face_chips)
+    AlignState align;
     // profiling
     bool profiling = false;
     std::map<std::string, ProfEntry> prof;
@@ -433,6 +436,7 @@ int pf_create(int device_id, pf_handle** out) {
     }
     if constexpr (PF_ABLATE != 0) {      // ablation build only (libpeppa_hip_ablate.so): ablated kernels compute garbage, so the guard is off
         if (const char* v = getenv("PEPPA_DBG")) { h->dbg = atoi(v); if (h->dbg & PF_DBG_GUARD_OFF_MASK) h->range_every = 0; }   // which bits leave results right: pf_ablate.h
+        if (const char* v = getenv("PEPPA_ALIGN_LDS")) h->align.lds_budget = atoi(v);     // 0: every align_warp tile takes the direct path (tools/bench_face_chips.py)
         if (const char* v = getenv("PEPPA_DET_TILE")) { if (sscanf(v, "%d,%d", &g_det_tile_th, &g_det_tile_tw) != 2) g_det_tile_th = g_det_tile_tw = 0; }
     }
     bool masked = false;
@@ -482,6 +486,7 @@ void pf_destroy(pf_handle* h) {
     if (h->d_dbg) { print_cycle_counters(h); (void)hipFree(h->d_dbg); }
     if (h->h_status) (void)hipHostFree(h->h_status);
     h->pipe.release();
+    h->align.release();
     h->track.release();
     h->streams.release();
     h->jpeg.release();
@@ -502,7 +507,7 @@ int pf_sync(pf_handle* h) {
 int pf_load_program(pf_handle* h, int slot, const void* blob, size_t bytes, int max_batch) {
     if (!h) return 1;
     if (slot < 0 || slot >= PF_NET_SLOTS) PF_FAIL(h, "slot %d out of range", slot);
-    if (slot == PF_NET_LANDMARK) h->attr_kind = 0;       // the records of the previous program are gone with its arena
+    if (slot == PF_NET_LANDMARK) { h->attr_kind = 0; h->align.kind = 0; }      // the records of the previous program are gone with its arena
     if (!blob || bytes < sizeof(PfHeader)) PF_FAIL(h, "program blob too small");
     if (max_batch < 1) PF_FAIL(h, "max_batch must be >= 1");
     PF_HIP(h, hipSetDevice(h->device));
@@ -590,6 +595,7 @@ int pf_landmark_forward(pf_handle* h, const void* input, int input_kind, int mem
     h->pipe.d_kps_for_decode = nullptr;
     begin_call(h);
     h->attr_kind = 0;
+    h->align.kind = 2;            // rows without a frame (pf_face_chips)
     if (net_forward_common(h, PF_NET_LANDMARK, input, input_kind, mem, batch, input_kind == PF_INPUT_U8_NHWC ? px : px * 4)) return 1;
     h->attr_kind = 1; h->attr_rows = batch;
     if (copy_out(h, p.buf_ptr(p.hdr.out_buf0), loc_fix, (size_t)batch * p.buf_item_bytes(p.hdr.out_buf0), out_mem)) return 1;
@@ -725,6 +731,7 @@ int pf_profile_fetch(pf_handle* h, char* names, size_t names_cap, float* ms, int
 
 }  // extern "C"
 
+#include "align.inl"
 #include "pipeline.inl"
 #include "comm.inl"
 #include "track.inl"

@@ -180,6 +180,7 @@ static int track_frame_impl(pf_handle* h, const uint8_t* bgr, int mem, int heigh
                             int* n_out, double* boxes, double* kps, float* scores, int* detector_ran) {
     if (!h) return 1;
     h->attr_kind = 0;
+    h->align.kind = 0;
     Program& det = h->prog[PF_NET_DETECTOR];
     Program& lm = h->prog[PF_NET_LANDMARK];
     if (!det.loaded || !lm.loaded) PF_FAIL(h, "pf_track_frame: detector and landmark programs must be loaded");
@@ -228,6 +229,8 @@ static int track_frame_impl(pf_handle* h, const uint8_t* bgr, int mem, int heigh
     n = std::min(n, top_k);
     *n_out = n;
     if (lm.hdr.out_buf2 >= 0) { h->attr_kind = 3; h->attr_src = h->d_track_attrs; h->attr_rows = n; }   // rows [n], like kps
+    // pf_face_chips: the n compacted faces, their smoothed float64 landmarks, the resident frame
+    chips_note_frames(h, h->pipe.d_cur, 0, 1, height, width, width * 3, n, top_k, P.v.out_lm, 1, nullptr);
     if (n > 0) {
         if (boxes) memcpy(boxes, hb.data(), (size_t)n * 4 * sizeof(double));
         if (kps) memcpy(kps, hk.data(), (size_t)n * 196 * sizeof(double));
@@ -243,6 +246,7 @@ int pf_track_streams_config(pf_handle* h, int max_streams, int top_k) {
     if (max_streams < 1 || top_k < 1) PF_FAIL(h, "pf_track_streams_config: bad arguments (max_streams %d, top_k %d)", max_streams, top_k);
     PF_HIP(h, hipSetDevice(h->device));
     TrackPool& P = h->streams;
+    h->align.kind = 0;
     if (track_pool_alloc(h, P, max_streams, top_k)) return 1;
     PF_HIP(h, hipMalloc((void**)&P.d_sums, (size_t)max_streams * sizeof(unsigned long long)));
     PF_HIP(h, hipMalloc((void**)&P.d_det_idx, (size_t)max_streams * sizeof(int)));
@@ -267,6 +271,7 @@ int pf_track_streams(pf_handle* h, int n, const int* stream_ids, const uint8_t* 
                      int* counts, double* boxes, double* kps, float* scores, int* detector_ran) {
     if (!h) return 1;
     h->attr_kind = 0;
+    h->align.kind = 0;
     TrackPool& P = h->streams;
     // every check before anything changes: a rejected call leaves every stream as it was
     if (P.S == 0) PF_FAIL(h, "pf_track_streams: no stream pool (call pf_track_streams_config first)");
@@ -352,6 +357,9 @@ int pf_track_streams(pf_handle* h, int n, const int* stream_ids, const uint8_t* 
         return 1;
     }
     if (lm.hdr.out_buf2 >= 0) { h->attr_kind = 3; h->attr_src = h->d_track_attrs; h->attr_rows = n * K; }   // rows [n][K], like kps
+    // pf_face_chips: rows [n][K]; frame i is read from its stream's slot, where the gate stored it
+    chips_note_frames(h, P.d_frames, 0, n, height, width, width * 3, n * K, K, P.v.out_lm, 1, P.v.out_count);
+    for (int i = 0; i < n; ++i) h->align.frames[i].base = P.d_frames + (size_t)stream_ids[i] * P.frame_slot_bytes;
     return 0;
 }
 

@@ -349,7 +349,14 @@ enum { PF_OPT_HIP_GRAPH = 1,
         * NMS / top-k ONCE, on all of its frames, on the batch's front engine, and the lanes run crop + landmarks of their slices
         * behind it (the detector's launches are latency-bound: 96 frames cost 2.3 x what 32 do).  0: every lane detects its own
         * slice (the only path for host-resident frames). */
-       PF_OPT_BATCH_FRONT = 5 };
+       PF_OPT_BATCH_FRONT = 5,
+       /* Testing and tuning switch, per handle.  0 (default): the engine chooses the TH x TW output tile of every workgroup-level
+        * detector launch (det_unit_kernel, det_c3_kernel) from the map, the batch and the device's compute units.  th << 16 | tw
+        * forces that tile (cut to the map where the map is smaller) for all of them.  A tile whose input region does not fit the
+        * LDS rows of a kernel the program launches makes the forward call fail with a message before anything is launched: it
+        * never falls back to another tile.  Results do not depend on the tile; speed does.  Captured graphs are dropped on a
+        * change. */
+       PF_OPT_DET_TILE = 6 };
 int pf_set_option(pf_handle* h, int option, int value);
 
 /* Per-kernel device time of the last call, accumulated with HIP events on the handle's stream
@@ -357,8 +364,9 @@ int pf_set_option(pf_handle* h, int option, int value);
 int pf_profile_enable(pf_handle* h, int on);
 int pf_profile_fetch(pf_handle* h, char* names, size_t names_cap, float* ms, int* counts, int cap, int* n_out);
 /* Kernels launched by the engine since profiling was enabled (nothing is recorded while it is off), in launch order: '\n'-separated
- * names as the launch sites spell them, template arguments included, e.g. "(conv3x3_halo_split_kernel<48, 8, 1, 256>)".  For tests
- * of the dispatch.  At most names_cap - 1 bytes are written; *bytes_needed is the size that holds everything, *n_out the number
+ * names as the launch sites spell them, template arguments included, e.g. "(conv3x3_halo_split_kernel<48, 8, 1, 256>)".  The
+ * det_unit_kernel / det_c3_kernel entries are followed by their run-time tile, tiles per frame and grid: " tile=6x5 tpf=40 grid=80".
+ * For tests of the dispatch.  At most names_cap - 1 bytes are written; *bytes_needed is the size that holds everything, *n_out the number
  * of launches (the log keeps the first 65536).  pf_profile_enable clears it. */
 int pf_launch_log(pf_handle* h, char* names, size_t names_cap, int* n_out, size_t* bytes_needed);
 

@@ -19,7 +19,13 @@ PF_OPT_HIP_GRAPH = 1
 PF_OPT_RANGE_CHECK = 2
 PF_OPT_JPEG_ENTROPY, PF_OPT_JPEG_SYNC_ROUNDS = 3, 4       # entropy decoding: 0 automatic / 1 host / 2 device; sync rounds 1..10 (0 = all)
 PF_OPT_BATCH_FRONT = 5      # BatchEngine.set_option only: 1 (default) detector + NMS once per call on the front engine, 0 per lane
+PF_OPT_DET_TILE = 6         # testing / tuning: 0 the engine picks the det_unit / det_c3 tile, th << 16 | tw forces it (det_tile_option)
 PF_COMM_ID_BYTES = 128
+
+
+def det_tile_option(th: int, tw: int) -> int:
+    """Value of ``PF_OPT_DET_TILE`` that forces a th x tw tile."""
+    return (int(th) << 16) | int(tw)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIBRARY = os.path.join(_HERE, "libpeppa_hip.so")

@@ -110,6 +110,7 @@ struct pf_handle {
     int range_every = 1;
     int jpeg_entropy = 0;               // PF_OPT_JPEG_ENTROPY: 0 automatic, 1 host, 2 device (jpeg.inl)
     int jpeg_rounds = 0;                // PF_OPT_JPEG_SYNC_ROUNDS: 0 = all PF_JPEG_SYNC_ROUNDS
+    int det_tile = 0;                   // PF_OPT_DET_TILE: 0 = det_pick_tile chooses, th << 16 | tw = that tile for the det_unit / det_c3 launches
     unsigned long long n_calls = 0;
     int* h_status = nullptr;            // page-locked, device-visible: {code, op, value bits, program slot}
     // RCCL communicator for pf_broadcast_weights (comm.inl); created lazily, one per handle
@@ -131,7 +132,7 @@ struct pf_handle {
     bool profiling = false;
     std::map<std::string, ProfEntry> prof;
     std::vector<std::string> prof_order;
-    std::vector<const char*> launch_log;      // spelled-out kernel of every PF_LAUNCH made while profiling is on (pf_launch_log)
+    std::vector<std::string> launch_log;      // spelled-out kernel of every PF_LAUNCH made while profiling is on, + its PF_LAUNCH_NOTE (pf_launch_log)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
@@ -151,7 +152,8 @@ namespace { void comm_release(pf_handle* h); }   // comm.inl
 
 // Launch log (pf_launch_log): while profiling is on, every PF_LAUNCH leaves the kernel as it is spelled at the launch site, template
 // arguments included ("(conv3x3_halo_split_kernel<48, 8, 1, 256>)"), so that a test of the dispatch knows which instance ran.
-// Off otherwise: one predictable branch per launch.  mbx_launch.cpp (its own translation unit) is not logged.
+// Off otherwise: one predictable branch per launch.  mbx_launch.cpp (its own translation unit) is not logged.  PF_LAUNCH_NOTE, right
+// behind a PF_LAUNCH, appends run-time facts of that launch to its entry (" tile=6x5 tpf=40 grid=80" of the det_* kernels).
 constexpr size_t PF_LAUNCH_LOG_CAP = 1 << 16;
 
 // every kernel launch is checked where it is made: a bad launch configuration (too much LDS, too many
@@ -163,6 +165,15 @@ constexpr size_t PF_LAUNCH_LOG_CAP = 1 << 16;
         hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__);                                     \
         const hipError_t _le = hipGetLastError();                                                            \
         if (_le != hipSuccess) PF_FAIL(h, "launch of %s failed: %s (%s:%d)", #kernel, hipGetErrorString(_le), __FILE__, __LINE__); \
+    } while (0)
+
+#define PF_LAUNCH_NOTE(...)                                                                                  \
+    do {                                                                                                     \
+        if (h->profiling && !h->launch_log.empty() && h->launch_log.size() < PF_LAUNCH_LOG_CAP) {            \
+            char _n[96];                                                                                     \
+            snprintf(_n, sizeof(_n), __VA_ARGS__);                                                           \
+            h->launch_log.back() += _n;                                                                      \
+        }                                                                                                    \
     } while (0)
 
 #define PF_HIP(h, call)                                                                        \
@@ -289,6 +300,7 @@ static int run_program_t(pf_handle* h, int slot, const void* d_input, int input_
     Program& p = h->prog[slot];
     constexpr bool F32 = std::is_same<T, float>::value;
     const bool guard = SPLIT && h->range_every > 0 && p.d_range != nullptr;     // every call, graph-captured ones included
+    if (SPLIT && h->det_tile && det_forced_tile_fits(h, p)) return 1;           // PF_OPT_DET_TILE: refused before the first launch
     for (size_t oi = 0; oi < p.ops.size(); ++oi) {
         const PfOpRec& op = p.ops[oi];
         unsigned* const rs = guard ? p.d_range + oi * PF_RANGE_OP_WORDS : nullptr;
@@ -693,7 +705,7 @@ int pf_profile_enable(pf_handle* h, int on) {
 int pf_launch_log(pf_handle* h, char* names, size_t names_cap, int* n_out, size_t* bytes_needed) {
     if (!h) return 1;
     std::string joined;
-    for (const char* k : h->launch_log) {
+    for (const std::string& k : h->launch_log) {
         joined += k;
         joined += '\n';
     }

@@ -1,4 +1,41 @@
 // Launchers of the detector's ops (k_det.h).  Included by engine.cpp only.
+
+// LDS rows (MAXR) of the det_unit_kernel / det_c3_kernel instance an op runs on, 0 if there is none; the PF_DETUNIT_CASE / PF_DETC3_CASE
+// tables below are asserted against these
+constexpr int det_unit_maxr(int C, int S) {
+    return S == 1 ? (C == 32 ? 256 : C == 64 ? 128 : C == 128 ? 144 : 0) : S == 2 ? (C == 32 ? 480 : C == 64 ? 256 : C == 128 ? 128 : 0) : 0;
+}
+constexpr int det_c3_maxr(int CIN, int tail) { return CIN == 192 && tail == 1 ? 128 : CIN == 128 && tail == 2 ? 176 : 0; }
+
+// PF_OPT_DET_TILE: the forced tile replaces the picker's choice (cut to the map like the ablation build's PEPPA_DET_TILE); one whose
+// region does not fit is an error, here and -- for the whole program, before its first launch -- in det_forced_tile_fits
+static int det_forced_tile(pf_handle* h, const char* what, int S, int max_rows, int outH, int outW, int* TH, int* TW) {
+    if (!h->det_tile) return 0;
+    const int th = h->det_tile >> 16, tw = h->det_tile & 0xffff;
+    const long long rows = ((long long)(th - 1) * S + 3) * ((long long)(tw - 1) * S + 3);      // th < 2^15, tw < 2^16: not an int product
+    if (th < 1 || tw < 1 || rows > max_rows)
+        PF_FAIL(h, "PF_OPT_DET_TILE: tile %dx%d needs a region of %lld rows, %s holds %d", th, tw, rows, what, max_rows);
+    *TH = std::min(th, outH); *TW = std::min(tw, outW);
+    return 0;
+}
+
+static int det_forced_tile_fits(pf_handle* h, const Program& p) {
+    int th = 0, tw = 0;
+    char what[64];
+    for (const PfOpRec& op : p.ops) {
+        if (op.code == PF_OP_DETUNIT) {
+            const PfDetunitOp& o = op.as<PfDetunitOp>();
+            snprintf(what, sizeof(what), "det_unit_kernel<%d, %d, %d>", o.C, o.K1, o.stride);
+            if (det_unit_maxr(o.C, o.stride) && det_forced_tile(h, what, o.stride, det_unit_maxr(o.C, o.stride), 1 << 16, 1 << 16, &th, &tw)) return 1;
+        } else if (op.code == PF_OP_DETC3) {
+            const PfDetc3Op& o = op.as<PfDetc3Op>();
+            snprintf(what, sizeof(what), "det_c3_kernel<%d, %d>", o.CIN, o.tail);
+            if (det_c3_maxr(o.CIN, o.tail) && det_forced_tile(h, what, 1, det_c3_maxr(o.CIN, o.tail), 1 << 16, 1 << 16, &th, &tw)) return 1;
+        }
+    }
+    return 0;
+}
+
 static int launch_detunit(pf_handle* h, const Program& p, const PfDetunitOp& o, int B, unsigned* range_slot) {
     const PfTensorRec& ti = p.tens[o.in_t];
     const PfTensorRec& to = p.tens[o.out_t];
@@ -24,9 +61,12 @@ static int launch_detunit(pf_handle* h, const Program& p, const PfDetunitOp& o, 
     ProfScope ps(h, "unit_s%d_c%d_%dx%d", S, C, to.H, to.W);
 #define PF_DETUNIT_CASE(CC, KK, SS, MAXR, NTHR, PERCU)                                                             \
     if (C == CC && K1 == KK && S == SS) {                                                                          \
+        static_assert(det_unit_maxr(CC, SS) == MAXR, "det_unit_maxr");                                             \
         det_pick_tile(h->num_cus, to.H, to.W, SS, MAXR, B, PERCU, &a.TH, &a.TW);                                               \
+        if (det_forced_tile(h, "det_unit_kernel<" #CC ", " #KK ", " #SS ">", SS, MAXR, to.H, to.W, &a.TH, &a.TW)) return 1; \
         a.tilesX = pf_div_up(to.W, a.TW); a.tpf = a.tilesX * pf_div_up(to.H, a.TH);                                 \
         PF_LAUNCH((det_unit_kernel<CC, KK, SS, MAXR, NTHR, PERCU * NTHR / 256>), dim3(a.tpf * B), dim3(NTHR), h->stream, a); \
+        PF_LAUNCH_NOTE(" tile=%dx%d tpf=%d grid=%d", a.TH, a.TW, a.tpf, a.tpf * B);                                \
     } else
     PF_DETUNIT_CASE(32, 32, 1, 256, 512, 2)
     PF_DETUNIT_CASE(64, 64, 1, 128, 512, 2)
@@ -66,9 +106,12 @@ static int launch_detc3(pf_handle* h, const Program& p, const PfDetc3Op& o, int 
     ProfScope ps(h, "c3_c%d_t%d_%dx%d", CIN, tail, a.H, a.W);
 #define PF_DETC3_CASE(CC, TT, MAXR, NTHR)                                                                          \
     if (CIN == CC && tail == TT) {                                                                                 \
+        static_assert(det_c3_maxr(CC, TT) == MAXR, "det_c3_maxr");                                                 \
         det_pick_tile(h->num_cus, a.H, a.W, 1, MAXR, B, 1, &a.TH, &a.TW);                                                      \
+        if (det_forced_tile(h, "det_c3_kernel<" #CC ", " #TT ">", 1, MAXR, a.H, a.W, &a.TH, &a.TW)) return 1;     \
         a.tilesX = pf_div_up(a.W, a.TW); a.tpf = a.tilesX * pf_div_up(a.H, a.TH);                                   \
         PF_LAUNCH((det_c3_kernel<CC, TT, MAXR, NTHR>), dim3(a.tpf * B), dim3(NTHR), h->stream, a); \
+        PF_LAUNCH_NOTE(" tile=%dx%d tpf=%d grid=%d", a.TH, a.TW, a.tpf, a.tpf * B);                                \
     } else
     PF_DETC3_CASE(192, 1, 128, 512)
     PF_DETC3_CASE(128, 2, 176, 512)

@@ -385,6 +385,12 @@ int pf_set_option(pf_handle* h, int option, int value) {
         h->range_every = value;                                        // 0 = off, anything else = every forward
         return 0;
     }
+    if (option == PF_OPT_DET_TILE) {
+        if (value < 0 || (value != 0 && ((value >> 16) < 1 || (value & 0xffff) < 1))) PF_FAIL(h, "PF_OPT_DET_TILE: 0 (the engine chooses) or th << 16 | tw with th, tw >= 1");
+        if (value != h->det_tile && h->graphs.note_realloc(h->err)) return 1;      // captured graphs carry the grids and the tile arguments: recapture
+        h->det_tile = value;
+        return 0;
+    }
     if (option == PF_OPT_JPEG_ENTROPY) {
         if (value < 0 || value > 2) PF_FAIL(h, "PF_OPT_JPEG_ENTROPY: 0 (automatic), 1 (host) or 2 (device)");
         h->jpeg_entropy = value;

@@ -113,6 +113,17 @@ def test_batch_errors_name_the_lane_emu(emu_library, student_weights):
     be.close()
 
 
+def test_batch_det_tile_option_reaches_every_engine_emu(emu_library):
+    """PF_OPT_DET_TILE through pf_batch_set_option: accepted, and a malformed value is refused by name (the lanes and the front engine
+    share pf_set_option, tests/test_op_conformance_det.py covers what the option does)."""
+    be = _native.BatchEngine(0, 2, emu_library)
+    be.set_option(_native.PF_OPT_DET_TILE, _native.det_tile_option(6, 5))
+    with pytest.raises(_native.PeppaHipError, match="lane 0: PF_OPT_DET_TILE"):
+        be.set_option(_native.PF_OPT_DET_TILE, 7)            # th = 0
+    be.set_option(_native.PF_OPT_DET_TILE, 0)
+    be.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("lanes", [2, 3])
 def test_bench_shape_96_frames_lanes_graph_pinned_matches_oracle(hip_library, student_weights, detector_weights, lanes):

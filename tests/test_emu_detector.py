@@ -1,4 +1,8 @@
-"""yolov5n-0.5 detector program on the CPU SIMT emulator vs the oracle restatement (small input)."""
+"""yolov5n-0.5 detector program on the CPU SIMT emulator vs the oracle restatement (small input).
+
+One 128 x 160 image at B = 1: the workgroup-level det_unit / det_c3 kernels of the f32s program see maps of 16 x 20, 8 x 10 and 4 x 5,
+on which the tile picker (256 emulated compute units) chooses 1 x 2 for the 16 x 20 maps and 1 x 1 for the others -- a wiring check
+of the whole graph.  The tiles production runs are covered kernel by kernel in tests/test_op_conformance_det.py."""
 import numpy as np
 import pytest
 import torch

@@ -27,7 +27,10 @@ def test_detector_384x640_matches_oracle(gpu_engine, detector_weights, dtype):
     assert info["rows"] == 15120                       # face_detector.py:31
     gpu_engine.load_program(1, blob, 2)
     img = sw.smooth_blob_images(2, 640, seed=9)[:, :384]
+    gpu_engine.profile_enable(True)
     rows = gpu_engine.detector_forward(img, 15120)
+    log = gpu_engine.launch_log()
+    gpu_engine.profile_enable(False)
     W = {k: torch.from_numpy(v) for k, v in detector_weights.items()}
     x = torch.from_numpy(img.astype(np.float32) / np.float32(255.0)).permute(0, 3, 1, 2).contiguous()
     taps = {}
@@ -39,6 +42,42 @@ def test_detector_384x640_matches_oracle(gpu_engine, detector_weights, dtype):
             g = gpu_engine.read_tensor(1, tid, 2, r.shape[1:])
             assert np.abs(g - r).max() / (np.abs(r).max() + 1e-9) < 2e-4, name
     assert np.abs(rows - ref).max() / np.abs(ref).max() < 2e-4
+    assert_predicted_det_tiles(log, 2, dtype)
+
+
+# det launches of the 384 x 640 detector in launch order: (instance of tests/det_tiles.py, output map, launches in a row)
+DET_LAUNCHES = [(("unit", 32, 16, 2), (48, 80), 1), (("unit", 32, 64, 1), (48, 80), 3), (("unit", 64, 64, 2), (24, 40), 1), (("unit", 64, 128, 1), (24, 40), 7),
+                (("unit", 128, 128, 2), (12, 20), 1), (("unit", 128, 256, 1), (12, 20), 3), (("c3", 192, 1), (24, 40), 1), (("c3", 128, 2), (48, 80), 1),
+                (("c3", 128, 2), (24, 40), 1), (("c3", 128, 2), (12, 20), 1)]
+
+
+def assert_predicted_det_tiles(log, batch, dtype):
+    """Every det_unit / det_c3 launch of the log ran the tile tests/det_tiles.py predicts for this device (f32 programs have none)."""
+    from tests import det_tiles
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    want = []
+    for inst, (h, w), n in DET_LAUNCHES if dtype == "f32s" else []:
+        th, tw = det_tiles.pick(inst, cus, h, w, batch)
+        tpf = -(-h // th) * -(-w // tw)
+        want += [(det_tiles.kernel_name(inst), th, tw, tpf, tpf * batch)] * n
+    got = det_tiles.logged_tiles(log)
+    assert len(got) == len(want), (len(got), len(want))
+    for (entry, *ran), (kern, *predicted) in zip(got, want):
+        assert kern in entry and ran == predicted, "B = %d: %s ran tile/tpf/grid %s, predicted %s %s" % (batch, entry, ran, kern, predicted)
+
+
+@pytest.mark.parametrize("batch", [1, 5, 17, 32])
+def test_detector_384x640_runs_predicted_tiles(gpu_engine, detector_weights, batch):
+    """The tiles change with the batch (9 to 30 per kernel instance over B = 1 .. 32): predicted == logged at a few more of them."""
+    blob, info = build_detector_program(detector_weights, (384, 640), "f32s")
+    gpu_engine.load_program(1, blob, batch)
+    img = np.ascontiguousarray(np.broadcast_to(sw.smooth_blob_images(1, 640, seed=9)[:, :384], (batch, 384, 640, 3)))
+    gpu_engine.profile_enable(True)
+    rows = gpu_engine.detector_forward(img, 15120)
+    log = gpu_engine.launch_log()
+    gpu_engine.profile_enable(False)
+    assert np.isfinite(rows).all()
+    assert_predicted_det_tiles(log, batch, "f32s")
 
 
 @pytest.mark.parametrize("hw", [(1080, 1920), (2160, 3840), (720, 1280), (273, 410), (768, 1280)])

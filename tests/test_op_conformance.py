@@ -7,8 +7,9 @@ Tolerance, per case, from the reference's own error: e32 = max|ref32 - ref64| / 
 the same x.  Bound = max(4 e32, 8 * 2^-24) in f32s programs (split operands carry 22 significand bits against float32's 24) and
 max(2 e32, 8 * 2^-24) in f32 programs and for the non-MFMA ops (summation order only).  Every case prints one "OPCONF" line with e32,
 the bound and the engine's error (profiles/op_conformance_mi355x.txt is those lines from the MI355X).  The dispatch cases also assert
-which kernel instance ran (Engine.launch_log).  Not covered here: f16 programs, the detector's det_* fusions, mbx and front2 (they
-keep tests/test_fused_blocks.py, test_emu_detector.py, test_emu_landmark.py)."""
+which kernel instance ran (Engine.launch_log).  The detector's det_* fusions are held to the same rule, at every tile production
+picks, in tests/test_op_conformance_det.py.  Not covered here: f16 programs, mbx and front2 (they keep tests/test_fused_blocks.py
+and test_emu_landmark.py)."""
 import numpy as np
 import pytest
 
@@ -100,15 +101,16 @@ def assert_inputs_alive(x):
     assert (np.abs(x).reshape(x.shape[0], -1).max(1) > 0.05).all()
 
 
-def check_close(tag, got, ref_fn, factor, ref_floor=0.1):
-    """ref_fn(torch dtype) -> numpy float64 array shaped like `got`.  Prints the OPCONF line, then asserts the bound."""
+def check_close(tag, got, ref_fn, factor, ref_floor=0.1, eps_floor=EPS_FLOOR):
+    """ref_fn(torch dtype) -> numpy float64 array shaped like `got`.  Prints the OPCONF line, then asserts the bound.
+    ``eps_floor``: the bound's floor where a chain of stages has one of its own (tests/test_op_conformance_det.py)."""
     import torch
     ref64, ref32 = ref_fn(torch.float64), ref_fn(torch.float32)
     scale = np.abs(ref64).max()
     assert np.isfinite(ref64).all() and scale > ref_floor, (tag, scale)
     assert got.shape == ref64.shape, (tag, got.shape, ref64.shape)
     e32 = np.abs(ref32 - ref64).max() / scale
-    bound = max(factor * e32, EPS_FLOOR)
+    bound = max(factor * e32, eps_floor)
     err = np.abs(got - ref64).max() / scale
     print("OPCONF %-58s e32 %.3e bound %.3e err %.3e ratio %.3f" % (tag, e32, bound, err, err / bound))
     assert np.isfinite(got).all() and err <= bound, (tag, err, bound)

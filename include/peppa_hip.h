@@ -108,6 +108,48 @@ int pf_align_faces(pf_handle* h, const uint8_t* frames, int mem, int n_frames, i
  * asked than it left. */
 int pf_face_chips(pf_handle* h, int rows, int chip_size, uint8_t* chips, double* mats, int* valid, int out_mem);
 
+/* Face-region label maps: which pixels are face, and which part of the face, scan-converted on the device from the 98 landmarks
+ * alone (no frame is read).  Arithmetic (the specification, restated in numpy by tests/mask_ref.py): eight
+ * closed polygons over WFLW indices -- 1 face (0..32, 46..42, 37..33: jaw, then the upper brow lines backwards), 2 left brow
+ * (33..41), 3 right brow (42..50), 4 left eye (60..67), 5 right eye (68..75), 6 nose (51, 55..59), 7 lips (76..87), 8 inner mouth
+ * (88..95); a pixel's label is the highest-numbered region containing it, 0 where none does.  A slot is valid iff it is live (as for
+ * the chips) and landmarks 0..95 are finite; the pupils 96 / 97 are not used.  Each coordinate is taken as float64, clamped to
+ * [-65536, 65536] and rounded to 1/16 pixel, X = floor(16 x + 0.5); everything after is integer.  Even-odd rule, pixel centres at
+ * integer coordinates, half-open edges: an edge (Xa, Ya)-(Xb, Yb) with Ya < Yb is active on row py iff Ya <= 16 py < Yb, its
+ * threshold there is T = ceil((Xa (Yb - Ya) + (Xb - Xa)(16 py - Ya)) / (16 (Yb - Ya))), and (px, py) is inside a polygon iff the
+ * number of its active edges with px < T is odd.  An axis-aligned rectangle with integer corners fills exactly x0 <= px < x1,
+ * y0 <= py < y1; abutting polygons share no pixel; self-intersecting polygons are well defined.  LIMITS: hard edges, no feathering;
+ * the face polygon stops at the upper brow line, so the forehead is not covered.
+ *
+ * chip_size = 0, frame space: labels [F][H][W] uint8, every byte written (background 0).  Where faces of a frame overlap, the
+ * lowest valid slot that gives the pixel a non-zero label owns it.  owners (optional) [F][H][W] uint8: slot + 1, 0 for background;
+ * needs top_k <= 255.  boxes (optional) [F][top_k][4] int32 x0, y0, x1, y1 = ceil(min X / 16), ceil(min Y / 16), ceil(max X / 16),
+ * ceil(max Y / 16) over the 96 vertices, clipped to the frame: every pixel a face can own lies in x0 <= px < x1, y0 <= py < y1.
+ * Box rows of invalid slots are left untouched.  valid (optional) [F][top_k], every slot.
+ * chip_size = S (a multiple of 16 in [32, 256]), chip space: labels [F][top_k][S][S], one map per slot in the coordinates of that
+ * face's chip -- each vertex goes through the matrix pf_align_faces computes for the same landmarks (the same function, the same
+ * bits), ((a x - b y) + tx, (b x + a y) + ty) in float64 without fma contraction, before the clamp.  A slot is valid iff the
+ * landmarks are finite and the fit is valid; maps of invalid slots are left untouched.  owners and boxes must be NULL; height and
+ * width are ignored.
+ *
+ * pf_mask_faces is the stage-level entry: kps, kps_f64, kps_mem, counts and top_k as for pf_align_faces.  Device outputs
+ * (out_mem = PF_MEM_DEVICE) are enqueued on the handle's stream without a read-back; host outputs are produced in the handle's
+ * scratch, copied and synchronised. */
+int pf_mask_faces(pf_handle* h, int n_frames, int height, int width, const void* kps, int kps_f64, int kps_mem, const int* counts,
+                  int top_k, int chip_size, uint8_t* labels, uint8_t* owners, int* boxes, int* valid, int out_mem);
+/* The maps of the faces of the handle's last pipeline call; row semantics and refusals exactly those of pf_face_chips.  In frame
+ * space the maps cover ceil(rows / per_frame) frames of that call's frame size, per_frame being the call's top_k (after
+ * pf_landmarks* its box count: one frame).  It reads the landmarks, counts and live flags the call left in the handle's own
+ * buffers and NEVER a frame, so -- unlike pf_face_chips -- it also works after device frames the CALLER owns are gone.  The record
+ * itself is dropped by the same calls that drop it for the chips (pf_set_frame, a call that stages new frames, pf_load_program of the
+ * landmark slot): after those it fails like pf_face_chips.
+ * pf_face_masks_shape is part of the feature: the frame-space maps take the frame size and per-frame slot count of the LAST CALL,
+ * which pf_face_masks does not take as arguments, so a caller that sizes labels / owners from its own bookkeeping and gets it wrong
+ * is written past the end.  It reports labels (and owners) [n_frames][height][width] for `rows` rows, with the refusals of
+ * pf_face_masks (same record, same messages), and writes nothing else. */
+int pf_face_masks(pf_handle* h, int rows, int chip_size, uint8_t* labels, uint8_t* owners, int* boxes, int* valid, int out_mem);
+int pf_face_masks_shape(pf_handle* h, int rows, int* n_frames, int* height, int* width);
+
 /* Detector forward == session.run of yolov5n-0.5.onnx (face_detector.py:29-31):
  * input float32 NCHW [1][3][384][640] RGB/255 or uint8 NHWC letterboxed RGB;
  * output [rows][16] decoded rows (cx,cy,w,h,obj,10 landmark coords,cls), rows = 15120 at 384x640. */
@@ -325,6 +367,11 @@ int pf_batch_face_attrs(pf_batch* b, int rows, float* out, int raw, int out_mem)
 /* pf_face_chips of the lanes, gathered the same way: chips [n_frames][top_k][S][S][3] (mats, valid alike) of the last
  * pf_batch_run_frames, front mode on or off.  Device-resident frames of that call must still be alive. */
 int pf_batch_face_chips(pf_batch* b, int rows, int chip_size, uint8_t* chips, double* mats, int* valid, int out_mem);
+/* pf_face_masks of the lanes, gathered the same way: in frame space labels (owners) [n_frames][H][W] of the last
+ * pf_batch_run_frames, each lane filling the maps of its own frames; boxes, valid and the chip-space maps laid out like its kps. */
+int pf_batch_face_masks(pf_batch* b, int rows, int chip_size, uint8_t* labels, uint8_t* owners, int* boxes, int* valid, int out_mem);
+/* the shape query of pf_face_masks_shape for the lanes' gathered maps */
+int pf_batch_face_masks_shape(pf_batch* b, int rows, int* n_frames, int* height, int* width);
 
 /* Engine options.  PF_OPT_HIP_GRAPH = 1: pf_run_frames* calls whose buffers all live on the device are captured
  * into a hipGraph per distinct (pointers, shapes, thresholds) and replayed (launch-latency bound small batches). */

@@ -63,6 +63,14 @@ def _declare(lib):
         lib.pf_batch_face_chips.argtypes = [vp, i, i, vp, vp, vp, i]
         for name in ("pf_align_faces", "pf_face_chips", "pf_batch_face_chips"):
             getattr(lib, name).restype = i
+    if hasattr(lib, "pf_mask_faces"):      # likewise
+        lib.pf_mask_faces.argtypes = [vp, i, i, i, vp, i, i, vp, i, i, vp, vp, vp, vp, i]
+        lib.pf_face_masks.argtypes = [vp, i, i, vp, vp, vp, vp, i]
+        lib.pf_batch_face_masks.argtypes = [vp, i, i, vp, vp, vp, vp, i]
+        lib.pf_face_masks_shape.argtypes = [vp, i, ip, ip, ip]
+        lib.pf_batch_face_masks_shape.argtypes = [vp, i, ip, ip, ip]
+        for name in ("pf_mask_faces", "pf_face_masks", "pf_batch_face_masks", "pf_face_masks_shape", "pf_batch_face_masks_shape"):
+            getattr(lib, name).restype = i
     lib.pf_detect.argtypes = [vp, vp, i, i, i, i, f, f, fp, i, ip]
     lib.pf_landmarks.argtypes = [vp, vp, i, i, i, i, fp, i, fp, fp, ip]
     lib.pf_landmarks_f64.argtypes = [vp, vp, i, i, i, i, C.POINTER(C.c_double), i, fp, fp, ip]
@@ -152,6 +160,22 @@ def _ptr(a):
     if isinstance(a, int):
         return C.c_void_p(a)
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _last_call_masks(check, fn, fn_shape, handle, what, rows, chip_size, owners, boxes):
+    """Host-output pf_face_masks / pf_batch_face_masks: the frame-space maps take the shape the library reports for `rows`."""
+    S, rows = int(chip_size), int(rows)
+    valid = np.zeros((rows,), np.int32)
+    if S:
+        labels, own, box = np.zeros((rows, max(S, 0), max(S, 0)), np.uint8), None, None
+    else:
+        F, H, W = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(fn_shape(handle, rows, C.byref(F), C.byref(H), C.byref(W)), what)
+        labels = np.zeros((F.value, H.value, W.value), np.uint8)
+        own = np.zeros_like(labels) if owners else None
+        box = np.zeros((rows, 4), np.int32) if boxes else None
+    check(fn(handle, rows, S, _ptr(labels), _ptr(own), _ptr(box), _ptr(valid), PF_MEM_HOST), what)
+    return labels, own, box, valid.astype(bool)
 
 
 class DeviceFrame:
@@ -359,6 +383,55 @@ class Engine:
         """Same into device memory, enqueued on the handle's stream."""
         self._check(self.lib.pf_face_chips(self.h, int(rows), int(chip_size), _ptr(d_chips), _ptr(d_mats) if d_mats else None,
                                            _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE), "pf_face_chips")
+
+    # ---- face-region label maps (include/peppa_hip.h pf_mask_faces / pf_face_masks) ----------------------------------------------
+    def mask_faces(self, kps: np.ndarray, height: int = 0, width: int = 0, counts: Optional[np.ndarray] = None, chip_size: int = 0,
+                   owners: bool = True, boxes: bool = True, out=None):
+        """Face-region label maps from landmarks alone.  kps: float32 or float64 [F,top_k,98,2] (or [top_k,98,2] for one frame);
+        counts: [F] live slots per frame (None: all).  Frame space (``chip_size = 0``): (labels uint8 [F,height,width], owners uint8
+        like labels or None, boxes int32 [F,top_k,4] or None, valid bool [F,top_k]).  Chip space: (labels uint8 [F,top_k,S,S], None,
+        None, valid); maps of invalid slots, like box rows of invalid slots, are left as they were (zero, or what
+        ``out = (labels, owners, boxes)`` held)."""
+        k = np.asarray(kps)
+        k = np.ascontiguousarray(k, np.float64 if k.dtype == np.float64 else np.float32)
+        if k.ndim == 3:
+            k = k[None]
+        if k.ndim != 4 or k.shape[2:] != (98, 2):
+            raise ValueError("kps must be [F,top_k,98,2]")
+        F, K = k.shape[:2]
+        S, H, W = int(chip_size), int(height), int(width)
+        c = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
+        if out is not None:
+            labels, own, box = out
+        elif S:
+            labels, own, box = np.zeros((F, K, max(S, 0), max(S, 0)), np.uint8), None, None
+        else:
+            labels = np.zeros((F, max(H, 0), max(W, 0)), np.uint8)
+            own = np.zeros_like(labels) if owners else None
+            box = np.zeros((F, K, 4), np.int32) if boxes else None
+        valid = np.zeros((F, K), np.int32)
+        self._check(self.lib.pf_mask_faces(self.h, F, H, W, _ptr(k), 1 if k.dtype == np.float64 else 0, PF_MEM_HOST, _ptr(c), K, S,
+                                           _ptr(labels), _ptr(own), _ptr(box), _ptr(valid), PF_MEM_HOST), "pf_mask_faces")
+        return labels, own, box, valid.astype(bool)
+
+    def face_masks_shape(self, rows: int):
+        """(n_frames, height, width) of the frame-space maps ``rows`` rows of the handle's last pipeline call need."""
+        F, H, W = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self.lib.pf_face_masks_shape(self.h, int(rows), C.byref(F), C.byref(H), C.byref(W)), "pf_face_masks_shape")
+        return F.value, H.value, W.value
+
+    def face_masks(self, rows: int, chip_size: int = 0, owners: bool = True, boxes: bool = True):
+        """Label maps of the faces of the handle's last pf_landmarks / pf_run_frames / pf_track_frame / pf_track_streams call, in
+        that call's row order (include/peppa_hip.h pf_face_masks).  Frame space: (labels uint8 [F,H,W], owners or None, boxes int32
+        [rows,4] or None, valid bool [rows]); chip space: (labels uint8 [rows,S,S], None, None, valid)."""
+        return _last_call_masks(self._check, self.lib.pf_face_masks, self.lib.pf_face_masks_shape, self.h, "pf_face_masks", rows,
+                                chip_size, owners, boxes)
+
+    def face_masks_device(self, rows: int, chip_size: int, d_labels: int, d_owners: int = 0, d_boxes: int = 0, d_valid: int = 0):
+        """Same into device memory (sized by face_masks_shape in frame space), enqueued on the handle's stream."""
+        self._check(self.lib.pf_face_masks(self.h, int(rows), int(chip_size), _ptr(d_labels), _ptr(d_owners) if d_owners else None,
+                                           _ptr(d_boxes) if d_boxes else None, _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE),
+                    "pf_face_masks")
 
     def landmark_forward_device(self, d_input: int, kind: int, batch: int, d_loc: int = 0, d_score: int = 0):
         """Same on device pointers (bench): nothing crosses PCIe."""
@@ -850,6 +923,18 @@ class BatchEngine:
         """Same into device memory, enqueued on the lanes' streams."""
         self._check(self.lib.pf_batch_face_chips(self.b, int(rows), int(chip_size), _ptr(d_chips), _ptr(d_mats) if d_mats else None,
                                                  _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE), "pf_batch_face_chips")
+
+    def face_masks(self, rows: int, chip_size: int = 0, owners: bool = True, boxes: bool = True):
+        """Label maps of the last run_frames* call (include/peppa_hip.h pf_batch_face_masks), as ``Engine.face_masks`` returns them:
+        frame-space maps [F,H,W], boxes and valid laid out like its kps ([F * top_k])."""
+        return _last_call_masks(self._check, self.lib.pf_batch_face_masks, self.lib.pf_batch_face_masks_shape, self.b,
+                                "pf_batch_face_masks", rows, chip_size, owners, boxes)
+
+    def face_masks_device(self, rows: int, chip_size: int, d_labels: int, d_owners: int = 0, d_boxes: int = 0, d_valid: int = 0):
+        """Same into device memory, enqueued on the lanes' streams."""
+        self._check(self.lib.pf_batch_face_masks(self.b, int(rows), int(chip_size), _ptr(d_labels), _ptr(d_owners) if d_owners else None,
+                                                 _ptr(d_boxes) if d_boxes else None, _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE),
+                    "pf_batch_face_masks")
 
     def close(self):
         self._host.close()

@@ -20,15 +20,19 @@ from ...logger.logger import logger
 from ...graph.detector import build_detector_program
 from ...graph.student import build_student_program
 from ..smoother.lk import EmaFilter
-from .facer import _box_iou, _load_weights, get_cfg
+from .facer import _box_iou, _load_weights, attach_masks, get_cfg
 from .hip_model_base import _RANGE_ERR
 
 
 class FrameBatchRunner:
     def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, lanes: int = 3, frames_per_lane: int = 32,
                  device: Optional[int] = None, library: Optional[str] = None, graph: bool = True, top_k: Optional[int] = None,
-                 face_attributes: Optional[bool] = None, face_chips: Optional[int] = None):
-        """``face_chips`` (default: ``Engine.face_chips`` of Skps.yml, 0 = off): a chip size adds ``"chip"`` and ``"chip_matrix"`` to
+                 face_attributes: Optional[bool] = None, face_chips: Optional[int] = None,
+                 face_masks: Optional[bool] = None):
+        """``face_masks`` (default: ``Engine.face_masks`` of Skps.yml, false): ``"mask_box"`` and ``"mask"`` in every result dict as in
+        ``FaceAna``; the whole maps of the last ``run`` stay reachable as ``last_label_maps`` / ``last_owner_maps`` (uint8 [F,H,W]).
+
+        ``face_chips`` (default: ``Engine.face_chips`` of Skps.yml, 0 = off): a chip size adds ``"chip"`` and ``"chip_matrix"`` to
         every result dict as in ``FaceAna``.
 
         ``face_attributes`` (default: ``Engine.face_attributes`` of Skps.yml): every result dict also gets ``"pose"`` and
@@ -38,6 +42,8 @@ class FrameBatchRunner:
         eng_cfg = sk.get("Engine", {})
         self.face_attributes = bool(eng_cfg.get("face_attributes", False)) if face_attributes is None else bool(face_attributes)
         self.face_chips = int(eng_cfg.get("face_chips", 0) or 0) if face_chips is None else int(face_chips or 0)
+        self.face_masks = bool(eng_cfg.get("face_masks", False)) if face_masks is None else bool(face_masks)
+        self.last_label_maps = self.last_owner_maps = None
         self.device = int(eng_cfg.get("device", 0)) if device is None else int(device)
         self.dtype = eng_cfg.get("dtype", "f32s")
         root = pathlib.Path(__file__).resolve().parents[2]
@@ -102,7 +108,7 @@ class FrameBatchRunner:
         return self._guarded(self.engine.run_frames, frames, self.score_thrs, self.iou_thrs, self.min_face, self.top_k, planted_rows)
 
     def _run_with_extras(self, frames, planted_rows=None):
-        """run_frames + the attribute rows and / or chips of the same call ([F][top_k] rows, like kps)."""
+        """run_frames + the attribute rows, chips and / or label maps of the same call ([F][top_k] rows, like kps)."""
         r = self.engine.run_frames(frames, self.score_thrs, self.iou_thrs, self.min_face, self.top_k, planted_rows)
         F, K = r[0].shape[0], self.top_k
         attrs = self.engine.face_attrs(F * K).reshape(F, K, 7) if self.face_attributes else None
@@ -110,7 +116,11 @@ class FrameBatchRunner:
         if self.face_chips:
             c, m, v = self.engine.face_chips(F * K, self.face_chips)
             chips = (c.reshape((F, K) + c.shape[1:]), m.reshape(F, K, 2, 3), v.reshape(F, K))
-        return r + (attrs, chips)
+        masks = None
+        if self.face_masks:
+            lab, own, mb, mv = self.engine.face_masks(F * K)
+            masks = (lab, own, mb.reshape(F, K, 4), mv.reshape(F, K))
+        return r + (attrs, chips, masks)
 
     def _returned_boxes(self, det_boxes: np.ndarray, kps: np.ndarray) -> np.ndarray:
         """The 'box' a fresh ``FaceAna.run`` hands back (facer.py:81-84): not the detector's box but the hull of the face's
@@ -131,14 +141,15 @@ class FrameBatchRunner:
         the smoothed landmark hull like the reference's, the detector's own box rides along as 'det_box'."""
         frames = np.stack(frames) if isinstance(frames, (list, tuple)) else np.asarray(frames)
         out: List[List[Dict[str, np.ndarray]]] = []
+        all_labels, all_owners = [], []
         for s in range(0, frames.shape[0], self.max_frames):
             chunk = frames[s:s + self.max_frames]
-            attrs = chips = None
+            attrs = chips = masks = None
             planted = self._planted_rows(chunk) if self._planted_rows is not None else None
-            if self.face_attributes or self.face_chips:
+            if self.face_attributes or self.face_chips or self.face_masks:
                 if chunk.ndim != 4 or chunk.shape[-1] != 3 or chunk.dtype != np.uint8:
                     raise ValueError("frames must be uint8 [F,H,W,3]")
-                counts, boxes, kps, scores, attrs, chips = self._guarded(self._run_with_extras, chunk, planted)
+                counts, boxes, kps, scores, attrs, chips, masks = self._guarded(self._run_with_extras, chunk, planted)
             else:
                 counts, boxes, kps, scores = self.run_arrays(chunk, planted)
             for f in range(counts.shape[0]):
@@ -154,7 +165,13 @@ class FrameBatchRunner:
                         if chips[2][f, i]:
                             d["chip"] = chips[0][f, i].copy()
                             d["chip_matrix"] = chips[1][f, i].copy()
+                if masks is not None:
+                    attach_masks(res, masks[0][f], masks[1][f], masks[2][f], masks[3][f])
                 out.append(res)
+            if masks is not None:
+                all_labels.append(masks[0]); all_owners.append(masks[1])
+        if self.face_masks and all_labels:
+            self.last_label_maps, self.last_owner_maps = np.concatenate(all_labels), np.concatenate(all_owners)
         return out
 
     def close(self):

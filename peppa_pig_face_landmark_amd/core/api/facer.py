@@ -74,11 +74,28 @@ def _box_iou(a, b) -> float:
     return inter / (total - inter)
 
 
+def attach_masks(dicts, labels, owners, boxes, valid):
+    """Result dict i of a frame (slot i of its maps) gets "mask_box" and "mask": the labels cropped to the slot's box, pixels another
+    face owns set to 0.  An invalid slot or an empty box gets neither."""
+    for i, d in enumerate(dicts):
+        x0, y0, x1, y1 = (int(v) for v in boxes[i])
+        if valid[i] and x1 > x0 and y1 > y0:
+            d["mask_box"] = np.array([x0, y0, x1, y1], np.int32)
+            d["mask"] = np.where(owners[y0:y1, x0:x1] == i + 1, labels[y0:y1, x0:x1], 0).astype(np.uint8)
+
+
 class FaceAna:
     def __init__(self, verbose: bool = False, cfg: Optional[dict] = None, weights: Optional[dict] = None,
                  device: Optional[int] = None, library: Optional[str] = None, face_attributes: Optional[bool] = None,
-                 face_chips: Optional[int] = None):
-        """``face_chips`` (default: ``Engine.face_chips`` of Skps.yml, 0 = off): a chip size S (a multiple of 16 in [32, 256], e.g.
+                 face_chips: Optional[int] = None, face_masks: Optional[bool] = None):
+        """``face_masks`` (default: ``Engine.face_masks`` of Skps.yml, false): every result dict also carries ``"mask_box"`` (int32
+        x0, y0, x1, y1) and ``"mask"`` (uint8 [y1 - y0, x1 - x0]: the frame's face-region labels -- 1 face, 2 / 3 brows, 4 / 5 eyes,
+        6 nose, 7 lips, 8 inner mouth -- cropped to the box, pixels owned by another face set to 0), filled on the GPU from the
+        landmarks the result carries; a face whose box is empty or whose landmarks are not finite gets neither key.  The whole maps of
+        the last frame stay reachable as ``last_label_map`` / ``last_owner_map`` (uint8 [H,W]; owner = index in the result list + 1).
+        Hard edges, no feathering; the face polygon stops at the upper brow line.
+
+        ``face_chips`` (default: ``Engine.face_chips`` of Skps.yml, 0 = off): a chip size S (a multiple of 16 in [32, 256], e.g.
         112) makes every result dict also carry ``"chip"`` (uint8 [S,S,3], BGR: the face warped onto the ArcFace five-point template
         on the GPU, cut with the landmarks the result carries) and ``"chip_matrix"`` (float64 [2,3], frame -> chip); a face whose
         fit is degenerate gets neither key.  No anti-alias pre-filter is applied when the face is larger than the chip.
@@ -106,6 +123,8 @@ class FaceAna:
         self.device_tracking = bool(eng_cfg.get("device_tracking", False))
         self.face_attributes = bool(eng_cfg.get("face_attributes", False)) if face_attributes is None else bool(face_attributes)
         self.face_chips = int(eng_cfg.get("face_chips", 0) or 0) if face_chips is None else int(face_chips or 0)
+        self.face_masks = bool(eng_cfg.get("face_masks", False)) if face_masks is None else bool(face_masks)
+        self.last_label_map = self.last_owner_map = None
         self._planted_rows = None    # test instrument: callable returning decoded detector rows that replace the detector's own
         self._det_cfg = sk["Detect"]
         self.top_k = sk["Detect"]["topk"]
@@ -135,7 +154,8 @@ class FaceAna:
             def fn(*args):       # the attribute rows / chips of the tracked faces, compacted like kps (pf_face_attrs / pf_face_chips after pf_track_frame)
                 r = self.engine.track_frame(*args)
                 return r + (self.engine.face_attrs(len(r[0])) if self.face_attributes else None,
-                            self.engine.face_chips(len(r[0]), self.face_chips) if self.face_chips and len(r[0]) else None)
+                            self.engine.face_chips(len(r[0]), self.face_chips) if self.face_chips and len(r[0]) else None,
+                            self.engine.face_masks(len(r[0])) if self.face_masks and len(r[0]) else None)
             out = run_guarded(
                 [self.face_detector.model, self.face_landmark.model], fn, image, float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]),
                 float(self.min_face), int(self.top_k), float(self.iou_thres), float(self.alpha), float(self.diff_thres),
@@ -143,7 +163,7 @@ class FaceAna:
             boxes, kps, scores = out[:3]
             self.previous_image = image
             self.track_box = boxes
-            return self.to_dict(boxes, kps, scores, out[4], out[5])
+            return self.to_dict(boxes, kps, scores, out[4], out[5], self._keep_masks(out[6], image))
         diff = self.engine.set_frame(image)
         self.previous_image = image
         if diff is None or self.track_box is None or diff > self.diff_thres:
@@ -166,7 +186,22 @@ class FaceAna:
         if self.face_chips and len(landmarks):      # cut with the smoothed landmarks the result carries, from the resident frame
             c, m, v = self.engine.align_faces(None, np.asarray(landmarks)[None], chip_size=self.face_chips)
             chips = (c[0], m[0], v[0])
-        return self.to_dict(self.track_box, landmarks, states, attrs, chips)
+        masks = None
+        if self.face_masks and len(landmarks):      # filled from the smoothed landmarks the result carries
+            masks = self.engine.mask_faces(np.asarray(landmarks)[None], image.shape[0], image.shape[1])
+        return self.to_dict(self.track_box, landmarks, states, attrs, chips, self._keep_masks(masks, image))
+
+    def _keep_masks(self, masks, image):
+        """(labels [1,H,W], owners, boxes, valid) of Engine.mask_faces / face_masks -> the one frame's (labels, owners, boxes [n,4],
+        valid [n]), remembered as last_label_map / last_owner_map (all zero when the frame has no face)."""
+        if not self.face_masks:
+            return None
+        if masks is None:
+            self.last_label_map = np.zeros(tuple(image.shape[:2]), np.uint8)
+            self.last_owner_map = self.last_label_map.copy()
+            return None
+        self.last_label_map, self.last_owner_map = masks[0][0], masks[1][0]
+        return self.last_label_map, self.last_owner_map, masks[2].reshape(-1, 4), masks[3].reshape(-1)
 
     def imread(self, path_or_bytes, want_host: bool = True):
         """``cv2.imread(path)`` of the reference's demo (demo.py:76) for baseline JPEG files: the Huffman stream is decoded on
@@ -193,8 +228,10 @@ class FaceAna:
             return frame
 
     @staticmethod
-    def to_dict(bboxes, kps, states, attrs=None, chips=None):
-        """``chips``: (chips [n,S,S,3], matrices [n,2,3], valid [n]) of the same rows (Engine.face_chips / align_faces)."""
+    def to_dict(bboxes, kps, states, attrs=None, chips=None, masks=None):
+        """``chips``: (chips [n,S,S,3], matrices [n,2,3], valid [n]) of the same rows (Engine.face_chips / align_faces).
+        ``masks``: (labels [H,W], owners [H,W], boxes [>= n,4], valid [>= n]) of the rows' frame, row i being slot i
+        (Engine.face_masks / mask_faces)."""
         out = [{"box": bboxes[i], "kps": kps[i], "scores": states[i]} for i in range(len(bboxes))]
         if attrs is not None:
             for i, d in enumerate(out):
@@ -205,6 +242,8 @@ class FaceAna:
                 if chips[2][i]:
                     d["chip"] = chips[0][i].copy()
                     d["chip_matrix"] = chips[1][i].copy()
+        if masks is not None:
+            attach_masks(out, *masks)
         return out
 
     def diff_frames(self, previous_frame, image) -> bool:

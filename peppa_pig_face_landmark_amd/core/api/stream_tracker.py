@@ -23,8 +23,13 @@ from .hip_model_base import HIPEngine, run_guarded
 class StreamTracker:
     def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, max_streams: int = 8,
                  device: Optional[int] = None, library: Optional[str] = None, verbose: bool = False,
-                 face_attributes: Optional[bool] = None, face_chips: Optional[int] = None):
-        """``face_chips`` (default: ``Engine.face_chips`` of Skps.yml, 0 = off): a chip size adds ``"chip"`` and ``"chip_matrix"`` to
+                 face_attributes: Optional[bool] = None, face_chips: Optional[int] = None,
+                 face_masks: Optional[bool] = None):
+        """``face_masks`` (default: ``Engine.face_masks`` of Skps.yml, false): ``"mask_box"`` and ``"mask"`` in every result dict as in
+        ``FaceAna``; the whole maps of the last call stay reachable as ``last_label_maps`` / ``last_owner_maps`` (stream id -> uint8
+        [H,W]).
+
+        ``face_chips`` (default: ``Engine.face_chips`` of Skps.yml, 0 = off): a chip size adds ``"chip"`` and ``"chip_matrix"`` to
         every result dict as in ``FaceAna``.
 
         ``face_attributes`` (default: ``Engine.face_attributes`` of Skps.yml): every result dict also gets ``"pose"`` and
@@ -46,6 +51,9 @@ class StreamTracker:
 
         self.face_attributes = bool(eng_cfg.get("face_attributes", False)) if face_attributes is None else bool(face_attributes)
         self.face_chips = int(eng_cfg.get("face_chips", 0) or 0) if face_chips is None else int(face_chips or 0)
+        self.face_masks = bool(eng_cfg.get("face_masks", False)) if face_masks is None else bool(face_masks)
+        self.last_label_maps: Dict[int, np.ndarray] = {}
+        self.last_owner_maps: Dict[int, np.ndarray] = {}
         self.max_streams = int(max_streams)
         self.top_k = int(sk["Detect"]["topk"])
         self._det_cfg = sk["Detect"]
@@ -76,19 +84,26 @@ class StreamTracker:
 
         def call(*args):
             r = self.engine.track_streams(*args)
-            attrs = chips = None
+            attrs = chips = masks = None
             if self.face_attributes:
                 a = self.engine.face_attrs(len(r) * K)           # [n][top_k] rows, compacted like kps
                 attrs = [a[i * K:i * K + len(b)] for i, (b, _, _, _) in enumerate(r)]
             if self.face_chips:
                 c = self.engine.face_chips(len(r) * K, self.face_chips)      # the same rows
                 chips = [tuple(x[i * K:i * K + len(b)] for x in c) for i, (b, _, _, _) in enumerate(r)]
-            return r, attrs, chips
-        res, attrs, chips = run_guarded([self.detector, self.landmark], call, ids, batch,
+            if self.face_masks:
+                lab, own, mb, mv = self.engine.face_masks(len(r) * K)        # one map per listed stream, slots = the same rows
+                masks = [(lab[i], own[i], mb[i * K:(i + 1) * K], mv[i * K:(i + 1) * K]) for i in range(len(r))]
+            return r, attrs, chips, masks
+        res, attrs, chips, masks = run_guarded([self.detector, self.landmark], call, ids, batch,
                                  float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]), float(self.min_face),
                                  float(self.iou_thres), float(self.alpha), float(self.diff_thres), planted)
         self.last_detector_ran = {s: ran for s, (_, _, _, ran) in zip(ids, res)}   # did the gate run the detector
-        return {s: self.to_dict(b, k, sc, attrs[i] if attrs is not None else None, chips[i] if chips is not None else None)
+        if masks is not None:
+            self.last_label_maps = {s: m[0] for s, m in zip(ids, masks)}
+            self.last_owner_maps = {s: m[1] for s, m in zip(ids, masks)}
+        return {s: self.to_dict(b, k, sc, attrs[i] if attrs is not None else None, chips[i] if chips is not None else None,
+                                masks[i] if masks is not None else None)
                 for i, (s, (b, k, sc, _)) in enumerate(zip(ids, res))}
 
     to_dict = staticmethod(FaceAna.to_dict)

@@ -343,4 +343,41 @@ int pf_batch_face_chips(pf_batch* b, int rows, int chip_size, uint8_t* chips, do
     return 0;
 }
 
+/* pf_face_masks of the lanes, gathered the same way; in frame space lane i fills the maps of its own frames */
+static int batch_masks_check(pf_batch* b, int rows) {
+    if (b->attr_frames == 0) PF_BFAIL(b, "pf_batch_face_masks: no pf_batch_run_frames call has left face rows");
+    if (rows < 0 || rows > b->attr_frames * b->attr_top_k)
+        PF_BFAIL(b, "pf_batch_face_masks: %d rows asked, the last call left %d", rows, b->attr_frames * b->attr_top_k);
+    return 0;
+}
+
+int pf_batch_face_masks_shape(pf_batch* b, int rows, int* n_frames, int* height, int* width) {
+    if (!b) return 1;
+    if (!n_frames || !height || !width) PF_BFAIL(b, "pf_batch_face_masks_shape: bad arguments");
+    if (batch_masks_check(b, rows)) return 1;
+    if (pf_face_masks_shape(b->lane[0], 0, n_frames, height, width)) PF_BFAIL(b, "lane 0: %s", pf_last_error(b->lane[0]));
+    *n_frames = (rows + b->attr_top_k - 1) / b->attr_top_k;
+    return 0;
+}
+
+int pf_batch_face_masks(pf_batch* b, int rows, int chip_size, uint8_t* labels, uint8_t* owners, int* boxes, int* valid, int out_mem) {
+    if (!b) return 1;
+    char buf[160];
+    if (const char* why = mask_check(chip_size, b->attr_top_k, owners, boxes, buf, sizeof(buf))) PF_BFAIL(b, "pf_batch_face_masks: %s", why);
+    if (!labels || !align_out_mem_ok(out_mem)) PF_BFAIL(b, "pf_batch_face_masks: bad arguments");
+    if (batch_masks_check(b, rows)) return 1;
+    int F = 0, H = 0, W = 0;
+    if (!chip_size && pf_batch_face_masks_shape(b, rows, &F, &H, &W)) return 1;
+    const int L = (int)b->lane.size(), K = b->attr_top_k;
+    const int per = (b->attr_frames + L - 1) / L;
+    for (int i = 0; i < L; ++i) {
+        const int r0 = i * per * K, nr = std::min(rows - r0, std::min(per, b->attr_frames - i * per) * K);
+        if (nr <= 0) break;
+        const size_t m0 = chip_size ? (size_t)r0 * chip_size * chip_size : (size_t)i * per * H * W;      // lane i's first map
+        if (pf_face_masks(b->lane[i], nr, chip_size, labels + m0, owners ? owners + m0 : nullptr, boxes ? boxes + (size_t)r0 * 4 : nullptr,
+                          valid ? valid + r0 : nullptr, out_mem)) PF_BFAIL(b, "lane %d: %s", i, pf_last_error(b->lane[i]));
+    }
+    return 0;
+}
+
 }  // extern "C"

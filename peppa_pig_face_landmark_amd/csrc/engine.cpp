@@ -35,6 +35,7 @@
 #include "k_prepost.h"
 #include "k_track.h"
 #include "k_align.h"
+#include "k_mask.h"
 #include "pf_program.h"
 
 
@@ -128,6 +129,8 @@ struct pf_handle {
     float* d_track_attrs = nullptr; size_t track_attrs_bytes = 0;
     // aligned face chips (align.inl): scratch, and where the last pipeline call left frames / landmarks / live flags (pf_face_chips)
     AlignState align;
+    // face-region label maps (mask.inl): scratch; what the last call left is read from `align`
+    MaskState mask;
     // profiling
     bool profiling = false;
     std::map<std::string, ProfEntry> prof;
@@ -449,6 +452,7 @@ int pf_create(int device_id, pf_handle** out) {
     if constexpr (PF_ABLATE != 0) {      // ablation build only (libpeppa_hip_ablate.so): ablated kernels compute garbage, so the guard is off
         if (const char* v = getenv("PEPPA_DBG")) { h->dbg = atoi(v); if (h->dbg & PF_DBG_GUARD_OFF_MASK) h->range_every = 0; }   // which bits leave results right: pf_ablate.h
         if (const char* v = getenv("PEPPA_ALIGN_LDS")) h->align.lds_budget = atoi(v);     // 0: every align_warp tile takes the direct path (tools/bench_face_chips.py)
+        if (const char* v = getenv("PEPPA_MASK_NOCULL")) h->mask.no_cull = atoi(v) ? 1 : 0;       // 1: mask_fill evaluates every slot in every tile, no parity folding (tools/bench_face_masks.py)
         if (const char* v = getenv("PEPPA_DET_TILE")) { if (sscanf(v, "%d,%d", &g_det_tile_th, &g_det_tile_tw) != 2) g_det_tile_th = g_det_tile_tw = 0; }
     }
     bool masked = false;
@@ -499,6 +503,7 @@ void pf_destroy(pf_handle* h) {
     if (h->h_status) (void)hipHostFree(h->h_status);
     h->pipe.release();
     h->align.release();
+    h->mask.release();
     h->track.release();
     h->streams.release();
     h->jpeg.release();
@@ -744,6 +749,7 @@ int pf_profile_fetch(pf_handle* h, char* names, size_t names_cap, float* ms, int
 }  // extern "C"
 
 #include "align.inl"
+#include "mask.inl"
 #include "pipeline.inl"
 #include "comm.inl"
 #include "track.inl"

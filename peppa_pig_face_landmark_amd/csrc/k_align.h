@@ -63,9 +63,9 @@ struct AlignFitArgs {
     int* valid_out;           // optional [n]: every slot
 };
 
-__device__ __forceinline__ double pf_align_kp(const AlignFitArgs& a, int slot, int point, int xy) {
+__device__ __forceinline__ double pf_align_kp(const void* kps, int kps_f64, int slot, int point, int xy) {
     const size_t i = ((size_t)slot * 98 + point) * 2 + xy;
-    return a.kps_f64 ? reinterpret_cast<const double*>(a.kps)[i] : (double)reinterpret_cast<const float*>(a.kps)[i];
+    return kps_f64 ? reinterpret_cast<const double*>(kps)[i] : (double)reinterpret_cast<const float*>(kps)[i];
 }
 
 __device__ __forceinline__ bool pf_align_finite(double v) { return v - v == 0.0; }      // false for NaN and +-inf
@@ -101,6 +101,20 @@ __device__ inline int pf_align_fit(const double (*p)[2], int S, double* m, doubl
     return 1;
 }
 
+// the five points of slot `slot` (also read by mask_edges_kernel, k_mask.h: chip-space masks use the chips' matrix)
+__device__ inline void pf_align_points(const void* kps, int kps_f64, int slot, double (*p)[2]) {
+#pragma clang fp contract(off)
+    for (int xy = 0; xy < 2; ++xy) {
+        double e0 = 0.0, e1 = 0.0;
+        for (int k = 0; k < 8; ++k) { e0 += pf_align_kp(kps, kps_f64, slot, 60 + k, xy); e1 += pf_align_kp(kps, kps_f64, slot, 68 + k, xy); }
+        p[0][xy] = e0 / 8.0;                                    // eye contours, not the pupils 96 / 97: those follow the gaze
+        p[1][xy] = e1 / 8.0;
+        p[2][xy] = pf_align_kp(kps, kps_f64, slot, 54, xy);     // nose tip
+        p[3][xy] = pf_align_kp(kps, kps_f64, slot, 76, xy);     // mouth corners
+        p[4][xy] = pf_align_kp(kps, kps_f64, slot, 82, xy);
+    }
+}
+
 __global__ __launch_bounds__(64) void align_fit_kernel(AlignFitArgs a) {
 #pragma clang fp contract(off)
     const int i = blockIdx.x * 64 + threadIdx.x;
@@ -111,15 +125,7 @@ __global__ __launch_bounds__(64) void align_fit_kernel(AlignFitArgs a) {
     double m[6], inv[PF_ALIGN_REC];
     if (ok) {
         double p[5][2];
-        for (int xy = 0; xy < 2; ++xy) {
-            double e0 = 0.0, e1 = 0.0;
-            for (int k = 0; k < 8; ++k) { e0 += pf_align_kp(a, i, 60 + k, xy); e1 += pf_align_kp(a, i, 68 + k, xy); }
-            p[0][xy] = e0 / 8.0;                       // eye contours, not the pupils 96 / 97: those follow the gaze
-            p[1][xy] = e1 / 8.0;
-            p[2][xy] = pf_align_kp(a, i, 54, xy);      // nose tip
-            p[3][xy] = pf_align_kp(a, i, 76, xy);      // mouth corners
-            p[4][xy] = pf_align_kp(a, i, 82, xy);
-        }
+        pf_align_points(a.kps, a.kps_f64, i, p);
         ok = pf_align_fit(p, a.S, m, inv);
     }
     a.valid[i] = ok;

@@ -150,6 +150,40 @@ int pf_mask_faces(pf_handle* h, int n_frames, int height, int width, const void*
 int pf_face_masks(pf_handle* h, int rows, int chip_size, uint8_t* labels, uint8_t* owners, int* boxes, int* valid, int out_mem);
 int pf_face_masks_shape(pf_handle* h, int rows, int* n_frames, int* height, int* width);
 
+/* Face redaction (kernel redact_kernel, csrc/k_redact.h): out [F][H][W][3] packed BGR, EVERY byte written -- the
+ * pixels the label maps above select are filled, pixelated or box-blurred, every other pixel is its input byte for byte.  The
+ * arithmetic is specified exactly and is integer throughout, so every byte is reproducible.
+ * Selection.  The frame-space labels, owners, boxes and valid of pf_mask_faces are computed from the same landmarks, counts and live
+ * flags over ALL valid slots.  select (optional) [F][top_k] ints; NULL selects every slot.  Pixel (x, y) with label L and owner o is
+ * selected iff (a) bit L of label_mask is set and (L == 0 or select == NULL or select[o - 1] != 0), or (b) label_mask has
+ * PF_REDACT_BOX and some valid, selected slot with a clipped box x1 > x0, y1 > y0 has x0 - pad <= x < x1 + pad and
+ * y0 - pad <= y < y1 + pad.  Bit 0 is the background, bits 1..8 the labels of pf_mask_faces.  An unselected face that owns a
+ * pixel protects it from (a).
+ * Value of a selected pixel, per channel, always from the INPUT frame (never from an already redacted pixel):
+ *   PF_REDACT_FILL    byte c of colour (the low byte is channel 0); strength is ignored
+ *   PF_REDACT_MOSAIC  strength = cell size 4, 8 or 16; cells are aligned to the frame origin; with n the in-frame pixels of the
+ *                     pixel's cell (selected or not) and S their sum: (S + (n >> 1)) / n, integer division
+ *   PF_REDACT_BLUR    strength = radius r in [1, 32]; the window [x - r, x + r] x [y - r, y + r] clipped to the frame, n its
+ *                     pixel count, S its sum: (S + (n >> 1)) / n
+ * frames, mem (host, device, or PF_MEM_RESIDENT with one frame), kps, kps_f64, kps_mem, counts and top_k as for pf_align_faces;
+ * select lives in the memory of kps; valid (optional) [F][top_k] as for pf_mask_faces; pad in [0, 4096]; select needs top_k <= 255
+ * (owners are bytes).  out must not alias the frames.  Device output (out_mem = PF_MEM_DEVICE) is enqueued on the handle's stream
+ * without a read-back; host output is produced in the handle's scratch, copied and synchronised.  LIMITS: out of place only; no
+ * cells of 32, no radius above 32, no Gaussian or iterated blur, hard edges; the forehead and hair only as far as PF_REDACT_BOX
+ * with pad reaches. */
+enum { PF_REDACT_FILL = 0, PF_REDACT_MOSAIC = 1, PF_REDACT_BLUR = 2 };
+enum { PF_REDACT_BACKGROUND = 0x001, PF_REDACT_FACE_ALL = 0x1FE, PF_REDACT_BOX = 0x200 };
+int pf_redact_faces(pf_handle* h, const uint8_t* frames, int mem, int n_frames, int height, int width,
+                    const void* kps, int kps_f64, int kps_mem, const int* counts, const int* select, int top_k,
+                    int mode, int label_mask, int strength, int pad, unsigned colour,
+                    uint8_t* out, int* valid, int out_mem);
+/* The frames of the handle's last pipeline call, redacted: rows, refusals and messages exactly those of pf_face_chips (the per-stream
+ * frame slots after pf_track_streams and a row stride other than 3 W included).  out is [ceil(rows / per_frame)][H][W][3], the shape
+ * pf_face_masks_shape reports; select is [rows] in HOST memory.  It reads the frames again: device frames the CALLER owns must
+ * still be alive and unchanged, as for pf_face_chips.  rows == 0 succeeds and writes nothing. */
+int pf_face_redact(pf_handle* h, int rows, const int* select, int mode, int label_mask, int strength, int pad, unsigned colour,
+                   uint8_t* out, int* valid, int out_mem);
+
 /* Detector forward == session.run of yolov5n-0.5.onnx (face_detector.py:29-31):
  * input float32 NCHW [1][3][384][640] RGB/255 or uint8 NHWC letterboxed RGB;
  * output [rows][16] decoded rows (cx,cy,w,h,obj,10 landmark coords,cls), rows = 15120 at 384x640. */
@@ -372,6 +406,11 @@ int pf_batch_face_chips(pf_batch* b, int rows, int chip_size, uint8_t* chips, do
 int pf_batch_face_masks(pf_batch* b, int rows, int chip_size, uint8_t* labels, uint8_t* owners, int* boxes, int* valid, int out_mem);
 /* the shape query of pf_face_masks_shape for the lanes' gathered maps */
 int pf_batch_face_masks_shape(pf_batch* b, int rows, int* n_frames, int* height, int* width);
+/* pf_face_redact of the lanes, gathered the same way: out [n_frames][H][W][3] of the last pf_batch_run_frames (the shape
+ * pf_batch_face_masks_shape reports), each lane writing the frames it ran, front mode on or off; select [rows] in host memory, valid
+ * laid out like its kps.  Device-resident frames of that call must still be alive. */
+int pf_batch_face_redact(pf_batch* b, int rows, const int* select, int mode, int label_mask, int strength, int pad, unsigned colour,
+                         uint8_t* out, int* valid, int out_mem);
 
 /* Engine options.  PF_OPT_HIP_GRAPH = 1: pf_run_frames* calls whose buffers all live on the device are captured
  * into a hipGraph per distinct (pointers, shapes, thresholds) and replayed (launch-latency bound small batches). */

@@ -71,6 +71,13 @@ def _declare(lib):
         lib.pf_batch_face_masks_shape.argtypes = [vp, i, ip, ip, ip]
         for name in ("pf_mask_faces", "pf_face_masks", "pf_batch_face_masks", "pf_face_masks_shape", "pf_batch_face_masks_shape"):
             getattr(lib, name).restype = i
+    if hasattr(lib, "pf_redact_faces"):    # likewise
+        u = C.c_uint
+        lib.pf_redact_faces.argtypes = [vp, vp, i, i, i, i, vp, i, i, vp, vp, i, i, i, i, i, u, vp, vp, i]
+        lib.pf_face_redact.argtypes = [vp, i, vp, i, i, i, i, u, vp, vp, i]
+        lib.pf_batch_face_redact.argtypes = [vp, i, vp, i, i, i, i, u, vp, vp, i]
+        for name in ("pf_redact_faces", "pf_face_redact", "pf_batch_face_redact"):
+            getattr(lib, name).restype = i
     lib.pf_detect.argtypes = [vp, vp, i, i, i, i, f, f, fp, i, ip]
     lib.pf_landmarks.argtypes = [vp, vp, i, i, i, i, fp, i, fp, fp, ip]
     lib.pf_landmarks_f64.argtypes = [vp, vp, i, i, i, i, C.POINTER(C.c_double), i, fp, fp, ip]
@@ -176,6 +183,35 @@ def _last_call_masks(check, fn, fn_shape, handle, what, rows, chip_size, owners,
         box = np.zeros((rows, 4), np.int32) if boxes else None
     check(fn(handle, rows, S, _ptr(labels), _ptr(own), _ptr(box), _ptr(valid), PF_MEM_HOST), what)
     return labels, own, box, valid.astype(bool)
+
+
+PF_REDACT_FILL, PF_REDACT_MOSAIC, PF_REDACT_BLUR = 0, 1, 2
+PF_REDACT_BACKGROUND, PF_REDACT_FACE_ALL, PF_REDACT_BOX = 0x001, 0x1FE, 0x200
+_REDACT_MODES = {"fill": PF_REDACT_FILL, "mosaic": PF_REDACT_MOSAIC, "blur": PF_REDACT_BLUR}
+
+
+def _redact_args(mode, labels, strength, pad, colour):
+    """The five redaction parameters as the C ABI takes them; mode is "fill" / "mosaic" / "blur" or its number, colour an int
+    (the low byte is channel 0) or a (c0, c1, c2) tuple."""
+    m = _REDACT_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if isinstance(m, str):
+        raise ValueError("mode must be 'fill', 'mosaic' or 'blur' (got %r)" % (mode,))
+    if not isinstance(colour, (int, np.integer)):
+        c = [int(v) & 255 for v in colour]
+        colour = c[0] | (c[1] << 8) | (c[2] << 16)
+    return int(m), int(labels), int(strength), int(pad), C.c_uint(int(colour) & 0xFFFFFFFF)
+
+
+def _last_call_redact(check, fn, fn_shape, handle, what, rows, select, args):
+    """Host-output pf_face_redact / pf_batch_face_redact: the frames take the shape the library reports for `rows`."""
+    rows = int(rows)
+    F, H, W = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(fn_shape(handle, rows, C.byref(F), C.byref(H), C.byref(W)), what)
+    out = np.zeros((F.value, H.value, W.value, 3), np.uint8)
+    valid = np.zeros((rows,), np.int32)
+    sel = None if select is None else np.ascontiguousarray(select, np.int32).reshape(rows)
+    check(fn(handle, rows, _ptr(sel), *args, _ptr(out), _ptr(valid), PF_MEM_HOST), what)
+    return out, valid.astype(bool)
 
 
 class DeviceFrame:
@@ -432,6 +468,63 @@ class Engine:
         self._check(self.lib.pf_face_masks(self.h, int(rows), int(chip_size), _ptr(d_labels), _ptr(d_owners) if d_owners else None,
                                            _ptr(d_boxes) if d_boxes else None, _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE),
                     "pf_face_masks")
+
+    # ---- face redaction (include/peppa_hip.h pf_redact_faces / pf_face_redact) ----------------------------------------------------
+    def redact_faces(self, frames, kps: np.ndarray, counts: Optional[np.ndarray] = None, select: Optional[np.ndarray] = None,
+                     mode="mosaic", labels: int = PF_REDACT_FACE_ALL, strength: int = 16, pad: int = 0, colour=(0, 0, 0), out=None):
+        """Frames with the selected face pixels filled, pixelated or box-blurred, every other pixel untouched.  frames: uint8
+        [F,H,W,3] (or [H,W,3]), ``None`` for the resident frame of set_frame(), or ``(device pointer, F, H, W)``; kps: float32 or
+        float64 [F,top_k,98,2] (or [top_k,98,2]); counts: [F] live slots per frame (None: all); select: [F,top_k], non-zero = the
+        slot is redacted (None: all); mode "fill" / "mosaic" (strength = cell 4, 8, 16) / "blur" (strength = radius 1..32); labels:
+        bit L = label L of mask_faces, bit 0 the background, 0x200 the boxes grown by ``pad``.  Returns (out uint8 [F,H,W,3], valid
+        bool [F,top_k])."""
+        k = np.asarray(kps)
+        k = np.ascontiguousarray(k, np.float64 if k.dtype == np.float64 else np.float32)
+        if k.ndim == 3:
+            k = k[None]
+        if k.ndim != 4 or k.shape[2:] != (98, 2):
+            raise ValueError("kps must be [F,top_k,98,2]")
+        F, K = k.shape[:2]
+        if frames is None:
+            shp = getattr(self, "_resident_shape", None)
+            if shp is None:
+                raise PeppaHipError("no resident frame: call set_frame() first")
+            fptr, mem, nf, H, W, keep = None, PF_MEM_RESIDENT, F, shp[0], shp[1], None
+        elif isinstance(frames, tuple):
+            fptr, mem, (nf, H, W), keep = C.c_void_p(int(frames[0])), PF_MEM_DEVICE, (int(v) for v in frames[1:]), None
+        else:
+            keep = np.ascontiguousarray(frames)
+            if keep.ndim == 3:
+                keep = keep[None]
+            if keep.dtype != np.uint8 or keep.ndim != 4 or keep.shape[3] != 3:
+                raise ValueError("frames must be uint8 [F,H,W,3]")
+            fptr, mem, (nf, H, W) = _ptr(keep), PF_MEM_HOST, keep.shape[:3]
+        if nf != F:
+            raise ValueError("%d frames, landmarks of %d" % (nf, F))
+        c = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
+        sel = None if select is None else np.ascontiguousarray(select, np.int32).reshape(F, K)
+        if out is None:
+            out = np.zeros((F, H, W, 3), np.uint8)
+        valid = np.zeros((F, K), np.int32)
+        self._check(self.lib.pf_redact_faces(self.h, fptr, mem, F, H, W, _ptr(k), 1 if k.dtype == np.float64 else 0, PF_MEM_HOST, _ptr(c),
+                                             _ptr(sel), K, *_redact_args(mode, labels, strength, pad, colour), _ptr(out), _ptr(valid),
+                                             PF_MEM_HOST), "pf_redact_faces")
+        return out, valid.astype(bool)
+
+    def face_redact(self, rows: int, select: Optional[np.ndarray] = None, mode="mosaic", labels: int = PF_REDACT_FACE_ALL,
+                    strength: int = 16, pad: int = 0, colour=(0, 0, 0)):
+        """The frames of the handle's last pf_landmarks / pf_run_frames / pf_track_frame / pf_track_streams call with the faces of its
+        first ``rows`` rows redacted (include/peppa_hip.h pf_face_redact): (out uint8 [F,H,W,3], valid bool [rows]).  select: [rows].
+        Device frames the caller handed to that call must still be alive."""
+        return _last_call_redact(self._check, self.lib.pf_face_redact, self.lib.pf_face_masks_shape, self.h, "pf_face_redact", rows,
+                                 select, _redact_args(mode, labels, strength, pad, colour))
+
+    def face_redact_device(self, rows: int, d_out: int, select: Optional[np.ndarray] = None, mode="mosaic",
+                           labels: int = PF_REDACT_FACE_ALL, strength: int = 16, pad: int = 0, colour=(0, 0, 0), d_valid: int = 0):
+        """Same into device memory (sized by face_masks_shape), enqueued on the handle's stream."""
+        sel = None if select is None else np.ascontiguousarray(select, np.int32).reshape(int(rows))
+        self._check(self.lib.pf_face_redact(self.h, int(rows), _ptr(sel), *_redact_args(mode, labels, strength, pad, colour), _ptr(d_out),
+                                            _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE), "pf_face_redact")
 
     def landmark_forward_device(self, d_input: int, kind: int, batch: int, d_loc: int = 0, d_score: int = 0):
         """Same on device pointers (bench): nothing crosses PCIe."""
@@ -935,6 +1028,24 @@ class BatchEngine:
         self._check(self.lib.pf_batch_face_masks(self.b, int(rows), int(chip_size), _ptr(d_labels), _ptr(d_owners) if d_owners else None,
                                                  _ptr(d_boxes) if d_boxes else None, _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE),
                     "pf_batch_face_masks")
+
+    def redact_faces(self, frames, kps, **kw):
+        """Stage-level redaction on lane 0's engine (``Engine.redact_faces``)."""
+        return self.lane(0).redact_faces(frames, kps, **kw)
+
+    def face_redact(self, rows: int, select: Optional[np.ndarray] = None, mode="mosaic", labels: int = PF_REDACT_FACE_ALL,
+                    strength: int = 16, pad: int = 0, colour=(0, 0, 0)):
+        """The frames of the last run_frames* call, redacted (include/peppa_hip.h pf_batch_face_redact), as ``Engine.face_redact``
+        returns them: (out uint8 [F,H,W,3], valid bool [rows]); each lane writes the frames it ran."""
+        return _last_call_redact(self._check, self.lib.pf_batch_face_redact, self.lib.pf_batch_face_masks_shape, self.b,
+                                 "pf_batch_face_redact", rows, select, _redact_args(mode, labels, strength, pad, colour))
+
+    def face_redact_device(self, rows: int, d_out: int, select: Optional[np.ndarray] = None, mode="mosaic",
+                           labels: int = PF_REDACT_FACE_ALL, strength: int = 16, pad: int = 0, colour=(0, 0, 0), d_valid: int = 0):
+        """Same into device memory, enqueued on the lanes' streams."""
+        sel = None if select is None else np.ascontiguousarray(select, np.int32).reshape(int(rows))
+        self._check(self.lib.pf_batch_face_redact(self.b, int(rows), _ptr(sel), *_redact_args(mode, labels, strength, pad, colour),
+                                                  _ptr(d_out), _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE), "pf_batch_face_redact")
 
     def close(self):
         self._host.close()

@@ -20,7 +20,7 @@ from ...logger.logger import logger
 from ...graph.detector import build_detector_program
 from ...graph.student import build_student_program
 from ..smoother.lk import EmaFilter
-from .facer import _box_iou, _load_weights, attach_masks, get_cfg
+from .facer import _box_iou, _load_weights, attach_masks, get_cfg, redact_options
 from .hip_model_base import _RANGE_ERR
 
 
@@ -28,8 +28,11 @@ class FrameBatchRunner:
     def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, lanes: int = 3, frames_per_lane: int = 32,
                  device: Optional[int] = None, library: Optional[str] = None, graph: bool = True, top_k: Optional[int] = None,
                  face_attributes: Optional[bool] = None, face_chips: Optional[int] = None,
-                 face_masks: Optional[bool] = None):
-        """``face_masks`` (default: ``Engine.face_masks`` of Skps.yml, false): ``"mask_box"`` and ``"mask"`` in every result dict as in
+                 face_masks: Optional[bool] = None, redact: Optional[dict] = None):
+        """``redact`` (default: ``Engine.redact`` of Skps.yml, off): the dict of ``FaceAna``; ``last_redacted`` (uint8 [F,H,W,3])
+        keeps the frames of the last ``run`` with every face the results carry redacted, a frame without a face as a copy.
+
+        ``face_masks`` (default: ``Engine.face_masks`` of Skps.yml, false): ``"mask_box"`` and ``"mask"`` in every result dict as in
         ``FaceAna``; the whole maps of the last ``run`` stay reachable as ``last_label_maps`` / ``last_owner_maps`` (uint8 [F,H,W]).
 
         ``face_chips`` (default: ``Engine.face_chips`` of Skps.yml, 0 = off): a chip size adds ``"chip"`` and ``"chip_matrix"`` to
@@ -44,6 +47,8 @@ class FrameBatchRunner:
         self.face_chips = int(eng_cfg.get("face_chips", 0) or 0) if face_chips is None else int(face_chips or 0)
         self.face_masks = bool(eng_cfg.get("face_masks", False)) if face_masks is None else bool(face_masks)
         self.last_label_maps = self.last_owner_maps = None
+        self.redact = redact_options(redact, eng_cfg)
+        self.last_redacted = None
         self.device = int(eng_cfg.get("device", 0)) if device is None else int(device)
         self.dtype = eng_cfg.get("dtype", "f32s")
         root = pathlib.Path(__file__).resolve().parents[2]
@@ -120,7 +125,8 @@ class FrameBatchRunner:
         if self.face_masks:
             lab, own, mb, mv = self.engine.face_masks(F * K)
             masks = (lab, own, mb.reshape(F, K, 4), mv.reshape(F, K))
-        return r + (attrs, chips, masks)
+        redacted = self.engine.face_redact(F * K, **self.redact)[0] if self.redact else None
+        return r + (attrs, chips, masks, redacted)
 
     def _returned_boxes(self, det_boxes: np.ndarray, kps: np.ndarray) -> np.ndarray:
         """The 'box' a fresh ``FaceAna.run`` hands back (facer.py:81-84): not the detector's box but the hull of the face's
@@ -141,15 +147,15 @@ class FrameBatchRunner:
         the smoothed landmark hull like the reference's, the detector's own box rides along as 'det_box'."""
         frames = np.stack(frames) if isinstance(frames, (list, tuple)) else np.asarray(frames)
         out: List[List[Dict[str, np.ndarray]]] = []
-        all_labels, all_owners = [], []
+        all_labels, all_owners, all_redacted = [], [], []
         for s in range(0, frames.shape[0], self.max_frames):
             chunk = frames[s:s + self.max_frames]
-            attrs = chips = masks = None
+            attrs = chips = masks = redacted = None
             planted = self._planted_rows(chunk) if self._planted_rows is not None else None
-            if self.face_attributes or self.face_chips or self.face_masks:
+            if self.face_attributes or self.face_chips or self.face_masks or self.redact:
                 if chunk.ndim != 4 or chunk.shape[-1] != 3 or chunk.dtype != np.uint8:
                     raise ValueError("frames must be uint8 [F,H,W,3]")
-                counts, boxes, kps, scores, attrs, chips, masks = self._guarded(self._run_with_extras, chunk, planted)
+                counts, boxes, kps, scores, attrs, chips, masks, redacted = self._guarded(self._run_with_extras, chunk, planted)
             else:
                 counts, boxes, kps, scores = self.run_arrays(chunk, planted)
             for f in range(counts.shape[0]):
@@ -170,8 +176,12 @@ class FrameBatchRunner:
                 out.append(res)
             if masks is not None:
                 all_labels.append(masks[0]); all_owners.append(masks[1])
+            if redacted is not None:
+                all_redacted.append(redacted)
         if self.face_masks and all_labels:
             self.last_label_maps, self.last_owner_maps = np.concatenate(all_labels), np.concatenate(all_owners)
+        if all_redacted:
+            self.last_redacted = np.concatenate(all_redacted)
         return out
 
     def close(self):

@@ -84,11 +84,39 @@ def attach_masks(dicts, labels, owners, boxes, valid):
             d["mask"] = np.where(owners[y0:y1, x0:x1] == i + 1, labels[y0:y1, x0:x1], 0).astype(np.uint8)
 
 
+def redact_options(value, eng_cfg):
+    """The ``redact`` option of the classes: ``None`` -> ``Engine.redact`` of Skps.yml; a false value is off (``None`` is returned);
+    a dict gives any of "mode" ("fill" / "mosaic" / "blur"), "labels", "strength", "pad", "colour" over the defaults of
+    ``Engine.redact_faces``; ``True`` is those defaults."""
+    if value is None:
+        value = eng_cfg.get("redact", None)
+    if not value:
+        return None
+    opts = {"mode": "mosaic", "labels": _native.PF_REDACT_FACE_ALL, "strength": 16, "pad": 0, "colour": (0, 0, 0)}
+    if isinstance(value, dict):
+        unknown = set(value) - set(opts)
+        if unknown:
+            raise ValueError("redact: unknown keys %s" % sorted(unknown))
+        opts.update(value)
+    return opts
+
+
+def host_frame(image) -> np.ndarray:
+    """A copy of a frame as a numpy array (a DeviceFrame gives its host copy)."""
+    return np.array(image.numpy() if isinstance(image, _native.DeviceFrame) else image)
+
+
 class FaceAna:
     def __init__(self, verbose: bool = False, cfg: Optional[dict] = None, weights: Optional[dict] = None,
                  device: Optional[int] = None, library: Optional[str] = None, face_attributes: Optional[bool] = None,
-                 face_chips: Optional[int] = None, face_masks: Optional[bool] = None):
-        """``face_masks`` (default: ``Engine.face_masks`` of Skps.yml, false): every result dict also carries ``"mask_box"`` (int32
+                 face_chips: Optional[int] = None, face_masks: Optional[bool] = None, redact: Optional[dict] = None):
+        """``redact`` (default: ``Engine.redact`` of Skps.yml, off): a dict with any of ``"mode"`` ("fill" / "mosaic" / "blur"),
+        ``"labels"`` (bit L = face-region label L, bit 0 the background, 0x200 the face boxes grown by ``"pad"``), ``"strength"``
+        (mosaic cell 4 / 8 / 16, blur radius 1..32), ``"pad"`` and ``"colour"`` keeps ``last_redacted`` (uint8 [H,W,3]): the frame
+        with every face the result carries redacted on the GPU from its landmarks, every other pixel untouched; a frame without a
+        face comes back as a copy.  The result dicts are unchanged.
+
+        ``face_masks`` (default: ``Engine.face_masks`` of Skps.yml, false): every result dict also carries ``"mask_box"`` (int32
         x0, y0, x1, y1) and ``"mask"`` (uint8 [y1 - y0, x1 - x0]: the frame's face-region labels -- 1 face, 2 / 3 brows, 4 / 5 eyes,
         6 nose, 7 lips, 8 inner mouth -- cropped to the box, pixels owned by another face set to 0), filled on the GPU from the
         landmarks the result carries; a face whose box is empty or whose landmarks are not finite gets neither key.  The whole maps of
@@ -125,6 +153,8 @@ class FaceAna:
         self.face_chips = int(eng_cfg.get("face_chips", 0) or 0) if face_chips is None else int(face_chips or 0)
         self.face_masks = bool(eng_cfg.get("face_masks", False)) if face_masks is None else bool(face_masks)
         self.last_label_map = self.last_owner_map = None
+        self.redact = redact_options(redact, eng_cfg)
+        self.last_redacted = None
         self._planted_rows = None    # test instrument: callable returning decoded detector rows that replace the detector's own
         self._det_cfg = sk["Detect"]
         self.top_k = sk["Detect"]["topk"]
@@ -155,7 +185,8 @@ class FaceAna:
                 r = self.engine.track_frame(*args)
                 return r + (self.engine.face_attrs(len(r[0])) if self.face_attributes else None,
                             self.engine.face_chips(len(r[0]), self.face_chips) if self.face_chips and len(r[0]) else None,
-                            self.engine.face_masks(len(r[0])) if self.face_masks and len(r[0]) else None)
+                            self.engine.face_masks(len(r[0])) if self.face_masks and len(r[0]) else None,
+                            self.engine.face_redact(len(r[0]), **self.redact)[0] if self.redact and len(r[0]) else None)
             out = run_guarded(
                 [self.face_detector.model, self.face_landmark.model], fn, image, float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]),
                 float(self.min_face), int(self.top_k), float(self.iou_thres), float(self.alpha), float(self.diff_thres),
@@ -163,6 +194,7 @@ class FaceAna:
             boxes, kps, scores = out[:3]
             self.previous_image = image
             self.track_box = boxes
+            self._keep_redacted(out[7], image)
             return self.to_dict(boxes, kps, scores, out[4], out[5], self._keep_masks(out[6], image))
         diff = self.engine.set_frame(image)
         self.previous_image = image
@@ -189,7 +221,16 @@ class FaceAna:
         masks = None
         if self.face_masks and len(landmarks):      # filled from the smoothed landmarks the result carries
             masks = self.engine.mask_faces(np.asarray(landmarks)[None], image.shape[0], image.shape[1])
+        redacted = None
+        if self.redact and len(landmarks):          # from the resident frame, with the smoothed landmarks the result carries
+            redacted = self.engine.redact_faces(None, np.asarray(landmarks)[None], **self.redact)[0]
+        self._keep_redacted(redacted, image)
         return self.to_dict(self.track_box, landmarks, states, attrs, chips, self._keep_masks(masks, image))
+
+    def _keep_redacted(self, redacted, image):
+        """[1,H,W,3] of Engine.redact_faces / face_redact, or None when the frame has no face -> last_redacted."""
+        if self.redact:
+            self.last_redacted = host_frame(image) if redacted is None else redacted[0]
 
     def _keep_masks(self, masks, image):
         """(labels [1,H,W], owners, boxes, valid) of Engine.mask_faces / face_masks -> the one frame's (labels, owners, boxes [n,4],

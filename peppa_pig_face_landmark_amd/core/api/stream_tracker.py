@@ -16,7 +16,7 @@ import numpy as np
 
 from ... import _native
 from ...logger.logger import logger
-from .facer import FaceAna, _load_weights, get_cfg
+from .facer import FaceAna, _load_weights, get_cfg, redact_options
 from .hip_model_base import HIPEngine, run_guarded
 
 
@@ -24,8 +24,11 @@ class StreamTracker:
     def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, max_streams: int = 8,
                  device: Optional[int] = None, library: Optional[str] = None, verbose: bool = False,
                  face_attributes: Optional[bool] = None, face_chips: Optional[int] = None,
-                 face_masks: Optional[bool] = None):
-        """``face_masks`` (default: ``Engine.face_masks`` of Skps.yml, false): ``"mask_box"`` and ``"mask"`` in every result dict as in
+                 face_masks: Optional[bool] = None, redact: Optional[dict] = None):
+        """``redact`` (default: ``Engine.redact`` of Skps.yml, off): the dict of ``FaceAna``; ``last_redacted`` (stream id -> uint8
+        [H,W,3]) keeps the frames of the last call with every face the results carry redacted.
+
+        ``face_masks`` (default: ``Engine.face_masks`` of Skps.yml, false): ``"mask_box"`` and ``"mask"`` in every result dict as in
         ``FaceAna``; the whole maps of the last call stay reachable as ``last_label_maps`` / ``last_owner_maps`` (stream id -> uint8
         [H,W]).
 
@@ -52,6 +55,8 @@ class StreamTracker:
         self.face_attributes = bool(eng_cfg.get("face_attributes", False)) if face_attributes is None else bool(face_attributes)
         self.face_chips = int(eng_cfg.get("face_chips", 0) or 0) if face_chips is None else int(face_chips or 0)
         self.face_masks = bool(eng_cfg.get("face_masks", False)) if face_masks is None else bool(face_masks)
+        self.redact = redact_options(redact, eng_cfg)
+        self.last_redacted: Optional[Dict[int, np.ndarray]] = None
         self.last_label_maps: Dict[int, np.ndarray] = {}
         self.last_owner_maps: Dict[int, np.ndarray] = {}
         self.max_streams = int(max_streams)
@@ -84,7 +89,9 @@ class StreamTracker:
 
         def call(*args):
             r = self.engine.track_streams(*args)
-            attrs = chips = masks = None
+            attrs = chips = masks = redacted = None
+            if self.redact:
+                redacted = self.engine.face_redact(len(r) * K, **self.redact)[0]      # one frame per listed stream
             if self.face_attributes:
                 a = self.engine.face_attrs(len(r) * K)           # [n][top_k] rows, compacted like kps
                 attrs = [a[i * K:i * K + len(b)] for i, (b, _, _, _) in enumerate(r)]
@@ -94,11 +101,13 @@ class StreamTracker:
             if self.face_masks:
                 lab, own, mb, mv = self.engine.face_masks(len(r) * K)        # one map per listed stream, slots = the same rows
                 masks = [(lab[i], own[i], mb[i * K:(i + 1) * K], mv[i * K:(i + 1) * K]) for i in range(len(r))]
-            return r, attrs, chips, masks
-        res, attrs, chips, masks = run_guarded([self.detector, self.landmark], call, ids, batch,
+            return r, attrs, chips, masks, redacted
+        res, attrs, chips, masks, redacted = run_guarded([self.detector, self.landmark], call, ids, batch,
                                  float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]), float(self.min_face),
                                  float(self.iou_thres), float(self.alpha), float(self.diff_thres), planted)
         self.last_detector_ran = {s: ran for s, (_, _, _, ran) in zip(ids, res)}   # did the gate run the detector
+        if redacted is not None:
+            self.last_redacted = {s: redacted[i] for i, s in enumerate(ids)}
         if masks is not None:
             self.last_label_maps = {s: m[0] for s, m in zip(ids, masks)}
             self.last_owner_maps = {s: m[1] for s, m in zip(ids, masks)}

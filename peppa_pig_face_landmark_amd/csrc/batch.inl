@@ -380,4 +380,30 @@ int pf_batch_face_masks(pf_batch* b, int rows, int chip_size, uint8_t* labels, u
     return 0;
 }
 
+/* pf_face_redact of the lanes, gathered the same way: lane i writes the frames it ran */
+int pf_batch_face_redact(pf_batch* b, int rows, const int* select, int mode, int label_mask, int strength, int pad, unsigned colour,
+                         uint8_t* out, int* valid, int out_mem) {
+    if (!b) return 1;
+    char buf[200];
+    if (const char* why = redact_check(mode, label_mask, strength, pad, select, b->attr_top_k, out, buf, sizeof(buf)))
+        PF_BFAIL(b, "pf_batch_face_redact: %s", why);
+    if (!align_out_mem_ok(out_mem)) PF_BFAIL(b, "pf_batch_face_redact: bad out_mem %d", out_mem);
+    if (b->attr_frames == 0) PF_BFAIL(b, "pf_batch_face_redact: no pf_batch_run_frames call has left face rows");
+    if (rows < 0 || rows > b->attr_frames * b->attr_top_k)
+        PF_BFAIL(b, "pf_batch_face_redact: %d rows asked, the last call left %d", rows, b->attr_frames * b->attr_top_k);
+    if (rows == 0) return 0;
+    int F = 0, H = 0, W = 0;
+    if (pf_batch_face_masks_shape(b, rows, &F, &H, &W)) return 1;
+    const int L = (int)b->lane.size(), K = b->attr_top_k;
+    const int per = (b->attr_frames + L - 1) / L;
+    for (int i = 0; i < L; ++i) {
+        const int r0 = i * per * K, nr = std::min(rows - r0, std::min(per, b->attr_frames - i * per) * K);
+        if (nr <= 0) break;
+        if (pf_face_redact(b->lane[i], nr, select ? select + r0 : nullptr, mode, label_mask, strength, pad, colour,
+                           out + (size_t)i * per * H * W * 3, valid ? valid + r0 : nullptr, out_mem))
+            PF_BFAIL(b, "lane %d: %s", i, pf_last_error(b->lane[i]));
+    }
+    return 0;
+}
+
 }  // extern "C"

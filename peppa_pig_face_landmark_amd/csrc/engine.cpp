@@ -36,6 +36,7 @@
 #include "k_track.h"
 #include "k_align.h"
 #include "k_mask.h"
+#include "k_redact.h"
 #include "pf_program.h"
 
 
@@ -131,6 +132,8 @@ struct pf_handle {
     AlignState align;
     // face-region label maps (mask.inl): scratch; what the last call left is read from `align`
     MaskState mask;
+    // face redaction (redact.inl): the label maps it reads and the staging of host outputs
+    RedactState redact;
     // profiling
     bool profiling = false;
     std::map<std::string, ProfEntry> prof;
@@ -453,6 +456,7 @@ int pf_create(int device_id, pf_handle** out) {
         if (const char* v = getenv("PEPPA_DBG")) { h->dbg = atoi(v); if (h->dbg & PF_DBG_GUARD_OFF_MASK) h->range_every = 0; }   // which bits leave results right: pf_ablate.h
         if (const char* v = getenv("PEPPA_ALIGN_LDS")) h->align.lds_budget = atoi(v);     // 0: every align_warp tile takes the direct path (tools/bench_face_chips.py)
         if (const char* v = getenv("PEPPA_MASK_NOCULL")) h->mask.no_cull = atoi(v) ? 1 : 0;       // 1: mask_fill evaluates every slot in every tile, no parity folding (tools/bench_face_masks.py)
+        if (const char* v = getenv("PEPPA_REDACT_STAGE_ALL")) h->redact.stage_all = atoi(v) ? 1 : 0;       // 1: redact_kernel stages every tile through LDS, none is copied (tools/bench_face_redact.py)
         if (const char* v = getenv("PEPPA_DET_TILE")) { if (sscanf(v, "%d,%d", &g_det_tile_th, &g_det_tile_tw) != 2) g_det_tile_th = g_det_tile_tw = 0; }
     }
     bool masked = false;
@@ -504,6 +508,7 @@ void pf_destroy(pf_handle* h) {
     h->pipe.release();
     h->align.release();
     h->mask.release();
+    h->redact.release();
     h->track.release();
     h->streams.release();
     h->jpeg.release();
@@ -750,6 +755,7 @@ int pf_profile_fetch(pf_handle* h, char* names, size_t names_cap, float* ms, int
 
 #include "align.inl"
 #include "mask.inl"
+#include "redact.inl"
 #include "pipeline.inl"
 #include "comm.inl"
 #include "track.inl"

@@ -169,6 +169,33 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _kps_arg(kps):
+    """Landmarks as the C ABI takes them: (float32 or float64 [F,top_k,98,2], contiguous; its kps_f64 flag; F; top_k).
+    [top_k,98,2] is one frame."""
+    k = np.asarray(kps)
+    k = np.ascontiguousarray(k, np.float64 if k.dtype == np.float64 else np.float32)
+    if k.ndim == 3:
+        k = k[None]
+    if k.ndim != 4 or k.shape[2:] != (98, 2):
+        raise ValueError("kps must be [F,top_k,98,2]")
+    return k, 1 if k.dtype == np.float64 else 0, k.shape[0], k.shape[1]
+
+
+# ---- host outputs of the last-call accessors, shared by Engine (pf_face_*) and BatchEngine (pf_batch_face_*) -------------------------
+def _last_call_attrs(check, fn, handle, what, rows, raw):
+    out = np.zeros((int(rows), 7), np.float32)
+    check(fn(handle, int(rows), _ptr(out), 1 if raw else 0, PF_MEM_HOST), what)
+    return out
+
+
+def _last_call_chips(check, fn, handle, what, rows, chip_size, out=None):
+    S, rows = int(chip_size), int(rows)
+    chips, mats = out if out is not None else (np.zeros((rows, max(S, 0), max(S, 0), 3), np.uint8), np.zeros((rows, 2, 3), np.float64))
+    valid = np.zeros((rows,), np.int32)
+    check(fn(handle, rows, S, _ptr(chips), _ptr(mats), _ptr(valid), PF_MEM_HOST), what)
+    return chips, mats, valid.astype(bool)
+
+
 def _last_call_masks(check, fn, fn_shape, handle, what, rows, chip_size, owners, boxes):
     """Host-output pf_face_masks / pf_batch_face_masks: the frame-space maps take the shape the library reports for `rows`."""
     S, rows = int(chip_size), int(rows)
@@ -361,27 +388,15 @@ class Engine:
         """Face attributes [rows, 7] of the faces of the handle's last pf_landmark_forward / pf_landmarks / pf_run_frames /
         pf_track_frame / pf_track_streams call, in that call's row order (include/peppa_hip.h pf_face_attrs).  raw=True: Net's x (pose / 90, four logits); raw=False: pose in degrees
         (about x, y, z) then P(eye 60-67 closed), P(eye 68-75 closed), P(mouth closed), P(mouth wide open)."""
-        out = np.zeros((int(rows), 7), np.float32)
-        self._check(self.lib.pf_face_attrs(self.h, int(rows), _ptr(out), 1 if raw else 0, PF_MEM_HOST), "pf_face_attrs")
-        return out
+        return _last_call_attrs(self._check, self.lib.pf_face_attrs, self.h, "pf_face_attrs", rows, raw)
 
     def face_attrs_device(self, rows: int, d_out: int, raw: bool = False):
         """Same into device memory, enqueued on the handle's stream."""
         self._check(self.lib.pf_face_attrs(self.h, int(rows), _ptr(d_out), 1 if raw else 0, PF_MEM_DEVICE), "pf_face_attrs")
 
-    # ---- aligned face chips (include/peppa_hip.h pf_align_faces / pf_face_chips) -------------------------------------------------
-    def align_faces(self, frames, kps: np.ndarray, counts: Optional[np.ndarray] = None, chip_size: int = 112, out=None):
-        """Similarity-warped face chips.  frames: uint8 [F,H,W,3] (or [H,W,3]), ``None`` for the resident frame of set_frame(), or
-        ``(device pointer, F, H, W)``; kps: float32 or float64 [F,top_k,98,2] (or [top_k,98,2] for one frame); counts: [F] live slots
-        per frame (None: all).  Returns (chips uint8 [F,top_k,S,S,3], mats float64 [F,top_k,2,3] frame -> chip, valid bool [F,top_k]);
-        chips and matrices of invalid slots are left as they were (zero, or what ``out = (chips, mats)`` held)."""
-        k = np.asarray(kps)
-        k = np.ascontiguousarray(k, np.float64 if k.dtype == np.float64 else np.float32)
-        if k.ndim == 3:
-            k = k[None]
-        if k.ndim != 4 or k.shape[2:] != (98, 2):
-            raise ValueError("kps must be [F,top_k,98,2]")
-        F, K = k.shape[:2]
+    def _frames_arg(self, frames, F):
+        """``frames`` of align_faces / redact_faces, which must be the ``F`` frames the landmarks belong to: (pointer, mem, F, H, W,
+        the host array to keep alive over the call or None)."""
         if frames is None:
             shp = getattr(self, "_resident_shape", None)
             if shp is None:
@@ -398,22 +413,28 @@ class Engine:
             fptr, mem, (nf, H, W) = _ptr(keep), PF_MEM_HOST, keep.shape[:3]
         if nf != F:
             raise ValueError("%d frames, landmarks of %d" % (nf, F))
+        return fptr, mem, F, H, W, keep
+
+    # ---- aligned face chips (include/peppa_hip.h pf_align_faces / pf_face_chips) -------------------------------------------------
+    def align_faces(self, frames, kps: np.ndarray, counts: Optional[np.ndarray] = None, chip_size: int = 112, out=None):
+        """Similarity-warped face chips.  frames: uint8 [F,H,W,3] (or [H,W,3]), ``None`` for the resident frame of set_frame(), or
+        ``(device pointer, F, H, W)``; kps: float32 or float64 [F,top_k,98,2] (or [top_k,98,2] for one frame); counts: [F] live slots
+        per frame (None: all).  Returns (chips uint8 [F,top_k,S,S,3], mats float64 [F,top_k,2,3] frame -> chip, valid bool [F,top_k]);
+        chips and matrices of invalid slots are left as they were (zero, or what ``out = (chips, mats)`` held)."""
+        k, f64, F, K = _kps_arg(kps)
+        fptr, mem, F, H, W, _keep = self._frames_arg(frames, F)
         c = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
         S = int(chip_size)
         chips, mats = out if out is not None else (np.zeros((F, K, max(S, 0), max(S, 0), 3), np.uint8), np.zeros((F, K, 2, 3), np.float64))
         valid = np.zeros((F, K), np.int32)
-        self._check(self.lib.pf_align_faces(self.h, fptr, mem, F, H, W, _ptr(k), 1 if k.dtype == np.float64 else 0, PF_MEM_HOST,
-                                            _ptr(c), K, S, _ptr(chips), _ptr(mats), _ptr(valid), PF_MEM_HOST), "pf_align_faces")
+        self._check(self.lib.pf_align_faces(self.h, fptr, mem, F, H, W, _ptr(k), f64, PF_MEM_HOST, _ptr(c), K, S, _ptr(chips), _ptr(mats),
+                                            _ptr(valid), PF_MEM_HOST), "pf_align_faces")
         return chips, mats, valid.astype(bool)
 
     def face_chips(self, rows: int, chip_size: int = 112, out=None):
         """Chips of the faces of the handle's last pf_landmarks / pf_run_frames / pf_track_frame / pf_track_streams call, in that
         call's row order (include/peppa_hip.h pf_face_chips): (chips uint8 [rows,S,S,3], mats float64 [rows,2,3], valid bool [rows])."""
-        S, rows = int(chip_size), int(rows)
-        chips, mats = out if out is not None else (np.zeros((rows, max(S, 0), max(S, 0), 3), np.uint8), np.zeros((rows, 2, 3), np.float64))
-        valid = np.zeros((rows,), np.int32)
-        self._check(self.lib.pf_face_chips(self.h, rows, S, _ptr(chips), _ptr(mats), _ptr(valid), PF_MEM_HOST), "pf_face_chips")
-        return chips, mats, valid.astype(bool)
+        return _last_call_chips(self._check, self.lib.pf_face_chips, self.h, "pf_face_chips", rows, chip_size, out)
 
     def face_chips_device(self, rows: int, chip_size: int, d_chips: int, d_mats: int = 0, d_valid: int = 0):
         """Same into device memory, enqueued on the handle's stream."""
@@ -428,13 +449,7 @@ class Engine:
         like labels or None, boxes int32 [F,top_k,4] or None, valid bool [F,top_k]).  Chip space: (labels uint8 [F,top_k,S,S], None,
         None, valid); maps of invalid slots, like box rows of invalid slots, are left as they were (zero, or what
         ``out = (labels, owners, boxes)`` held)."""
-        k = np.asarray(kps)
-        k = np.ascontiguousarray(k, np.float64 if k.dtype == np.float64 else np.float32)
-        if k.ndim == 3:
-            k = k[None]
-        if k.ndim != 4 or k.shape[2:] != (98, 2):
-            raise ValueError("kps must be [F,top_k,98,2]")
-        F, K = k.shape[:2]
+        k, f64, F, K = _kps_arg(kps)
         S, H, W = int(chip_size), int(height), int(width)
         c = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
         if out is not None:
@@ -446,7 +461,7 @@ class Engine:
             own = np.zeros_like(labels) if owners else None
             box = np.zeros((F, K, 4), np.int32) if boxes else None
         valid = np.zeros((F, K), np.int32)
-        self._check(self.lib.pf_mask_faces(self.h, F, H, W, _ptr(k), 1 if k.dtype == np.float64 else 0, PF_MEM_HOST, _ptr(c), K, S,
+        self._check(self.lib.pf_mask_faces(self.h, F, H, W, _ptr(k), f64, PF_MEM_HOST, _ptr(c), K, S,
                                            _ptr(labels), _ptr(own), _ptr(box), _ptr(valid), PF_MEM_HOST), "pf_mask_faces")
         return labels, own, box, valid.astype(bool)
 
@@ -478,35 +493,14 @@ class Engine:
         slot is redacted (None: all); mode "fill" / "mosaic" (strength = cell 4, 8, 16) / "blur" (strength = radius 1..32); labels:
         bit L = label L of mask_faces, bit 0 the background, 0x200 the boxes grown by ``pad``.  Returns (out uint8 [F,H,W,3], valid
         bool [F,top_k])."""
-        k = np.asarray(kps)
-        k = np.ascontiguousarray(k, np.float64 if k.dtype == np.float64 else np.float32)
-        if k.ndim == 3:
-            k = k[None]
-        if k.ndim != 4 or k.shape[2:] != (98, 2):
-            raise ValueError("kps must be [F,top_k,98,2]")
-        F, K = k.shape[:2]
-        if frames is None:
-            shp = getattr(self, "_resident_shape", None)
-            if shp is None:
-                raise PeppaHipError("no resident frame: call set_frame() first")
-            fptr, mem, nf, H, W, keep = None, PF_MEM_RESIDENT, F, shp[0], shp[1], None
-        elif isinstance(frames, tuple):
-            fptr, mem, (nf, H, W), keep = C.c_void_p(int(frames[0])), PF_MEM_DEVICE, (int(v) for v in frames[1:]), None
-        else:
-            keep = np.ascontiguousarray(frames)
-            if keep.ndim == 3:
-                keep = keep[None]
-            if keep.dtype != np.uint8 or keep.ndim != 4 or keep.shape[3] != 3:
-                raise ValueError("frames must be uint8 [F,H,W,3]")
-            fptr, mem, (nf, H, W) = _ptr(keep), PF_MEM_HOST, keep.shape[:3]
-        if nf != F:
-            raise ValueError("%d frames, landmarks of %d" % (nf, F))
+        k, f64, F, K = _kps_arg(kps)
+        fptr, mem, F, H, W, _keep = self._frames_arg(frames, F)
         c = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
         sel = None if select is None else np.ascontiguousarray(select, np.int32).reshape(F, K)
         if out is None:
             out = np.zeros((F, H, W, 3), np.uint8)
         valid = np.zeros((F, K), np.int32)
-        self._check(self.lib.pf_redact_faces(self.h, fptr, mem, F, H, W, _ptr(k), 1 if k.dtype == np.float64 else 0, PF_MEM_HOST, _ptr(c),
+        self._check(self.lib.pf_redact_faces(self.h, fptr, mem, F, H, W, _ptr(k), f64, PF_MEM_HOST, _ptr(c),
                                              _ptr(sel), K, *_redact_args(mode, labels, strength, pad, colour), _ptr(out), _ptr(valid),
                                              PF_MEM_HOST), "pf_redact_faces")
         return out, valid.astype(bool)
@@ -994,9 +988,7 @@ class BatchEngine:
     def face_attrs(self, rows: int, raw: bool = False) -> np.ndarray:
         """Face attributes [rows, 7] of the last run_frames* call, laid out like its kps ([F * top_k]; include/peppa_hip.h
         pf_batch_face_attrs)."""
-        out = np.zeros((int(rows), 7), np.float32)
-        self._check(self.lib.pf_batch_face_attrs(self.b, int(rows), _ptr(out), 1 if raw else 0, PF_MEM_HOST), "pf_batch_face_attrs")
-        return out
+        return _last_call_attrs(self._check, self.lib.pf_batch_face_attrs, self.b, "pf_batch_face_attrs", rows, raw)
 
     def face_attrs_device(self, rows: int, d_out: int, raw: bool = False):
         """Same into device memory, enqueued on the lanes' streams."""
@@ -1005,12 +997,7 @@ class BatchEngine:
     def face_chips(self, rows: int, chip_size: int = 112):
         """Chips of the last run_frames* call, laid out like its kps ([F * top_k]; include/peppa_hip.h pf_batch_face_chips):
         (chips uint8 [rows,S,S,3], mats float64 [rows,2,3], valid bool [rows])."""
-        S, rows = int(chip_size), int(rows)
-        chips = np.zeros((rows, max(S, 0), max(S, 0), 3), np.uint8)
-        mats = np.zeros((rows, 2, 3), np.float64)
-        valid = np.zeros((rows,), np.int32)
-        self._check(self.lib.pf_batch_face_chips(self.b, rows, S, _ptr(chips), _ptr(mats), _ptr(valid), PF_MEM_HOST), "pf_batch_face_chips")
-        return chips, mats, valid.astype(bool)
+        return _last_call_chips(self._check, self.lib.pf_batch_face_chips, self.b, "pf_batch_face_chips", rows, chip_size)
 
     def face_chips_device(self, rows: int, chip_size: int, d_chips: int, d_mats: int = 0, d_valid: int = 0):
         """Same into device memory, enqueued on the lanes' streams."""

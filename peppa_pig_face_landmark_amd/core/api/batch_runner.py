@@ -20,7 +20,7 @@ from ...logger.logger import logger
 from ...graph.detector import build_detector_program
 from ...graph.student import build_student_program
 from ..smoother.lk import EmaFilter
-from .facer import _box_iou, _load_weights, attach_masks, get_cfg, redact_options
+from .facer import _box_iou, _load_weights, attach_masks, get_cfg, stage_options
 from .hip_model_base import _RANGE_ERR
 
 
@@ -43,11 +43,8 @@ class FrameBatchRunner:
         cfg = cfg or get_cfg()
         sk = cfg["Skps"]
         eng_cfg = sk.get("Engine", {})
-        self.face_attributes = bool(eng_cfg.get("face_attributes", False)) if face_attributes is None else bool(face_attributes)
-        self.face_chips = int(eng_cfg.get("face_chips", 0) or 0) if face_chips is None else int(face_chips or 0)
-        self.face_masks = bool(eng_cfg.get("face_masks", False)) if face_masks is None else bool(face_masks)
+        self.face_attributes, self.face_chips, self.face_masks, self.redact = stage_options(eng_cfg, face_attributes, face_chips, face_masks, redact)
         self.last_label_maps = self.last_owner_maps = None
-        self.redact = redact_options(redact, eng_cfg)
         self.last_redacted = None
         self.device = int(eng_cfg.get("device", 0)) if device is None else int(device)
         self.dtype = eng_cfg.get("dtype", "f32s")

@@ -101,6 +101,15 @@ def redact_options(value, eng_cfg):
     return opts
 
 
+def stage_options(eng_cfg, face_attributes=None, face_chips=None, face_masks=None, redact=None):
+    """The four options FaceAna, StreamTracker and FrameBatchRunner share, each from its argument or, when that is ``None``, from
+    ``Engine`` of Skps.yml: (face_attributes bool, face_chips int (0 = off), face_masks bool, redact dict or None)."""
+    return (bool(eng_cfg.get("face_attributes", False)) if face_attributes is None else bool(face_attributes),
+            int(eng_cfg.get("face_chips", 0) or 0) if face_chips is None else int(face_chips or 0),
+            bool(eng_cfg.get("face_masks", False)) if face_masks is None else bool(face_masks),
+            redact_options(redact, eng_cfg))
+
+
 def host_frame(image) -> np.ndarray:
     """A copy of a frame as a numpy array (a DeviceFrame gives its host copy)."""
     return np.array(image.numpy() if isinstance(image, _native.DeviceFrame) else image)
@@ -149,11 +158,8 @@ class FaceAna:
         # Engine.device_tracking: keep track_box / previous landmarks / One-Euro state on the GPU (pf_track_frame) instead of
         # walking the boxes through numpy between the two networks on every frame
         self.device_tracking = bool(eng_cfg.get("device_tracking", False))
-        self.face_attributes = bool(eng_cfg.get("face_attributes", False)) if face_attributes is None else bool(face_attributes)
-        self.face_chips = int(eng_cfg.get("face_chips", 0) or 0) if face_chips is None else int(face_chips or 0)
-        self.face_masks = bool(eng_cfg.get("face_masks", False)) if face_masks is None else bool(face_masks)
+        self.face_attributes, self.face_chips, self.face_masks, self.redact = stage_options(eng_cfg, face_attributes, face_chips, face_masks, redact)
         self.last_label_map = self.last_owner_map = None
-        self.redact = redact_options(redact, eng_cfg)
         self.last_redacted = None
         self._planted_rows = None    # test instrument: callable returning decoded detector rows that replace the detector's own
         self._det_cfg = sk["Detect"]

@@ -16,7 +16,7 @@ import numpy as np
 
 from ... import _native
 from ...logger.logger import logger
-from .facer import FaceAna, _load_weights, get_cfg, redact_options
+from .facer import FaceAna, _load_weights, get_cfg, stage_options
 from .hip_model_base import HIPEngine, run_guarded
 
 
@@ -52,10 +52,7 @@ class StreamTracker:
         kps_arch = str(sk["Keypoints"].get("model", "student"))
         kps_w = weights.get("keypoints") or _load_weights(root, sk["Keypoints"]["model_path"], "teacher" if kps_arch == "teacher" else "keypoints")
 
-        self.face_attributes = bool(eng_cfg.get("face_attributes", False)) if face_attributes is None else bool(face_attributes)
-        self.face_chips = int(eng_cfg.get("face_chips", 0) or 0) if face_chips is None else int(face_chips or 0)
-        self.face_masks = bool(eng_cfg.get("face_masks", False)) if face_masks is None else bool(face_masks)
-        self.redact = redact_options(redact, eng_cfg)
+        self.face_attributes, self.face_chips, self.face_masks, self.redact = stage_options(eng_cfg, face_attributes, face_chips, face_masks, redact)
         self.last_redacted: Optional[Dict[int, np.ndarray]] = None
         self.last_label_maps: Dict[int, np.ndarray] = {}
         self.last_owner_maps: Dict[int, np.ndarray] = {}

@@ -36,7 +36,7 @@ struct pf_batch {
     hipEvent_t ev_front[2] = {nullptr, nullptr};
     std::vector<hipEvent_t> ev_lane[2];      // lane i's tail of the last call of that parity
     bool ev_lane_live[2] = {false, false};
-    // the last successful pf_batch_run_frames (pf_batch_face_attrs): frames and top_k; lane i holds the records of its slice
+    // the last successful pf_batch_run_frames (pf_batch_face_*, batch_lanes): frames and top_k; lane i holds the records of its slice
     int attr_frames = 0, attr_top_k = 0;
     const int* last_sel_count = nullptr;     // front mode: the counts of that call (pf_batch_face_chips)
 };
@@ -48,6 +48,31 @@ struct pf_batch {
         (b)->err = _b;                                    \
         return 1;                                         \
     } while (0)
+
+// The two refusals every pf_batch_face_* call shares: no call has left rows (`what`: "face rows", "face-attribute rows"), and more
+// rows asked than it left.  args_ok = false (a NULL output of pf_batch_face_attrs / _chips) is reported as the latter.
+static int batch_rows_check(pf_batch* b, const char* who, const char* what, int rows, bool args_ok = true) {
+    if (b->attr_frames == 0) PF_BFAIL(b, "%s: no pf_batch_run_frames call has left %s", who, what);
+    if (!args_ok || rows < 0 || rows > b->attr_frames * b->attr_top_k)
+        PF_BFAIL(b, "%s: %d rows asked, the last call left %d", who, rows, b->attr_frames * b->attr_top_k);
+    return 0;
+}
+
+// The lane walker of the pf_batch_face_* calls: lane i holds the frames [i * per, ...) of the last pf_batch_run_frames and so the
+// rows [i * per * top_k, ...) of the call.  fn(lane, f0, r0, nr) serves rows [r0, r0 + nr) from the lane whose first frame is f0;
+// a lane's refusal is reported with its number.
+template <typename Fn>
+static int batch_lanes(pf_batch* b, const char* who, const char* what, int rows, bool args_ok, Fn&& fn) {
+    if (batch_rows_check(b, who, what, rows, args_ok)) return 1;
+    const int L = (int)b->lane.size(), K = b->attr_top_k;
+    const int per = (b->attr_frames + L - 1) / L;
+    for (int i = 0; i < L; ++i) {
+        const int f0 = i * per, r0 = f0 * K, nr = std::min(rows - r0, std::min(per, b->attr_frames - f0) * K);
+        if (nr <= 0) break;
+        if (fn(b->lane[i], f0, r0, nr)) PF_BFAIL(b, "lane %d: %s", i, pf_last_error(b->lane[i]));
+    }
+    return 0;
+}
 
 extern "C" {
 
@@ -257,7 +282,7 @@ int pf_batch_run_frames(pf_batch* b, const uint8_t* frames, int mem, int n_frame
     // every lane's share is checked BEFORE anything is enqueued: a lane that refuses its slice must not leave the lanes in front of
     // it writing into buffers the caller frees when the call fails
     b->attr_frames = 0;
-    for (pf_handle* h : b->lane) { h->attr_kind = 0; h->align.kind = 0; }
+    for (pf_handle* h : b->lane) h->last.forget();
     const Program& fdet = b->front->prog[PF_NET_DETECTOR];
     const bool front = b->front_mode && (mem & 0xff) == PF_MEM_DEVICE && (fdet.loaded ? n_frames <= fdet.max_batch : det_rows != nullptr);
     for (int i = 0; i < L; ++i) {
@@ -295,10 +320,10 @@ int pf_batch_run_frames(pf_batch* b, const uint8_t* frames, int mem, int n_frame
     for (int i = 0; i < L; ++i) {       // face-attribute rows: lane i holds [its frames][top_k] (enqueued, like the other outputs)
         const int nf = std::min(per, n_frames - i * per);
         if (nf <= 0) break;
-        b->lane[i]->attr_kind = 1; b->lane[i]->attr_rows = nf * top_k;
+        b->lane[i]->last.note_attrs(1, nf * top_k);
         if (front)       // pf_batch_face_chips (without the front engine pf_run_frames_planted has noted the lane's own slice)
-            chips_note_frames(b->lane[i], frames + (size_t)i * per * frame_bytes, frame_bytes, nf, height, width, width * 3, nf * top_k, top_k,
-                              b->lane[i]->pipe.d_kps, 0, b->last_sel_count + i * per);
+            b->lane[i]->last.note_frames(face_frames(frames + (size_t)i * per * frame_bytes, frame_bytes, nf, height, width, width * 3), nf * top_k,
+                                         top_k, b->lane[i]->pipe.d_kps, 0, b->last_sel_count + i * per);
     }
     b->attr_frames = n_frames; b->attr_top_k = top_k;
     if (out_mem != PF_MEM_HOST) return 0;
@@ -312,49 +337,27 @@ int pf_batch_run_frames(pf_batch* b, const uint8_t* frames, int mem, int n_frame
 
 int pf_batch_face_attrs(pf_batch* b, int rows, float* out, int raw, int out_mem) {
     if (!b) return 1;
-    if (b->attr_frames == 0) PF_BFAIL(b, "pf_batch_face_attrs: no pf_batch_run_frames call has left face-attribute rows");
-    const int L = (int)b->lane.size(), K = b->attr_top_k;
-    if (!out || rows < 0 || rows > b->attr_frames * K) PF_BFAIL(b, "pf_batch_face_attrs: %d rows asked, the last call left %d", rows, b->attr_frames * K);
-    const int per = (b->attr_frames + L - 1) / L;
-    for (int i = 0; i < L; ++i) {       // lane i's rows are rows [i * per * K, ...) of the call: the slices of pf_batch_run_frames
-        const int r0 = i * per * K, nr = std::min(rows - r0, std::min(per, b->attr_frames - i * per) * K);
-        if (nr <= 0) break;
-        if (pf_face_attrs(b->lane[i], nr, out + (size_t)r0 * 7, raw, out_mem)) PF_BFAIL(b, "lane %d: %s", i, pf_last_error(b->lane[i]));
-    }
-    return 0;
+    return batch_lanes(b, "pf_batch_face_attrs", "face-attribute rows", rows, out != nullptr,
+                       [&](pf_handle* h, int, int r0, int nr) { return pf_face_attrs(h, nr, out + (size_t)r0 * 7, raw, out_mem); });
 }
 
 /* pf_face_chips of the lanes, gathered like pf_batch_face_attrs: lane i cuts the chips of its slice of the last pf_batch_run_frames */
 int pf_batch_face_chips(pf_batch* b, int rows, int chip_size, uint8_t* chips, double* mats, int* valid, int out_mem) {
     if (!b) return 1;
     if (const char* why = align_check_size(chip_size)) PF_BFAIL(b, "pf_batch_face_chips: %s (got %d)", why, chip_size);
-    if (!align_out_mem_ok(out_mem)) PF_BFAIL(b, "pf_batch_face_chips: bad out_mem %d", out_mem);
-    if (b->attr_frames == 0) PF_BFAIL(b, "pf_batch_face_chips: no pf_batch_run_frames call has left face rows");
-    const int L = (int)b->lane.size(), K = b->attr_top_k;
-    if (!chips || rows < 0 || rows > b->attr_frames * K) PF_BFAIL(b, "pf_batch_face_chips: %d rows asked, the last call left %d", rows, b->attr_frames * K);
-    const int per = (b->attr_frames + L - 1) / L;
+    if (!face_out_mem_ok(out_mem)) PF_BFAIL(b, "pf_batch_face_chips: bad out_mem %d", out_mem);
     const size_t chip_bytes = (size_t)chip_size * chip_size * 3;
-    for (int i = 0; i < L; ++i) {
-        const int r0 = i * per * K, nr = std::min(rows - r0, std::min(per, b->attr_frames - i * per) * K);
-        if (nr <= 0) break;
-        if (pf_face_chips(b->lane[i], nr, chip_size, chips + (size_t)r0 * chip_bytes, mats ? mats + (size_t)r0 * 6 : nullptr,
-                          valid ? valid + r0 : nullptr, out_mem)) PF_BFAIL(b, "lane %d: %s", i, pf_last_error(b->lane[i]));
-    }
-    return 0;
+    return batch_lanes(b, "pf_batch_face_chips", "face rows", rows, chips != nullptr, [&](pf_handle* h, int, int r0, int nr) {
+        return pf_face_chips(h, nr, chip_size, chips + (size_t)r0 * chip_bytes, mats ? mats + (size_t)r0 * 6 : nullptr, valid ? valid + r0 : nullptr,
+                             out_mem);
+    });
 }
 
 /* pf_face_masks of the lanes, gathered the same way; in frame space lane i fills the maps of its own frames */
-static int batch_masks_check(pf_batch* b, int rows) {
-    if (b->attr_frames == 0) PF_BFAIL(b, "pf_batch_face_masks: no pf_batch_run_frames call has left face rows");
-    if (rows < 0 || rows > b->attr_frames * b->attr_top_k)
-        PF_BFAIL(b, "pf_batch_face_masks: %d rows asked, the last call left %d", rows, b->attr_frames * b->attr_top_k);
-    return 0;
-}
-
 int pf_batch_face_masks_shape(pf_batch* b, int rows, int* n_frames, int* height, int* width) {
     if (!b) return 1;
     if (!n_frames || !height || !width) PF_BFAIL(b, "pf_batch_face_masks_shape: bad arguments");
-    if (batch_masks_check(b, rows)) return 1;
+    if (batch_rows_check(b, "pf_batch_face_masks", "face rows", rows)) return 1;
     if (pf_face_masks_shape(b->lane[0], 0, n_frames, height, width)) PF_BFAIL(b, "lane 0: %s", pf_last_error(b->lane[0]));
     *n_frames = (rows + b->attr_top_k - 1) / b->attr_top_k;
     return 0;
@@ -364,20 +367,14 @@ int pf_batch_face_masks(pf_batch* b, int rows, int chip_size, uint8_t* labels, u
     if (!b) return 1;
     char buf[160];
     if (const char* why = mask_check(chip_size, b->attr_top_k, owners, boxes, buf, sizeof(buf))) PF_BFAIL(b, "pf_batch_face_masks: %s", why);
-    if (!labels || !align_out_mem_ok(out_mem)) PF_BFAIL(b, "pf_batch_face_masks: bad arguments");
-    if (batch_masks_check(b, rows)) return 1;
+    if (!labels || !face_out_mem_ok(out_mem)) PF_BFAIL(b, "pf_batch_face_masks: bad arguments");
     int F = 0, H = 0, W = 0;
-    if (!chip_size && pf_batch_face_masks_shape(b, rows, &F, &H, &W)) return 1;
-    const int L = (int)b->lane.size(), K = b->attr_top_k;
-    const int per = (b->attr_frames + L - 1) / L;
-    for (int i = 0; i < L; ++i) {
-        const int r0 = i * per * K, nr = std::min(rows - r0, std::min(per, b->attr_frames - i * per) * K);
-        if (nr <= 0) break;
-        const size_t m0 = chip_size ? (size_t)r0 * chip_size * chip_size : (size_t)i * per * H * W;      // lane i's first map
-        if (pf_face_masks(b->lane[i], nr, chip_size, labels + m0, owners ? owners + m0 : nullptr, boxes ? boxes + (size_t)r0 * 4 : nullptr,
-                          valid ? valid + r0 : nullptr, out_mem)) PF_BFAIL(b, "lane %d: %s", i, pf_last_error(b->lane[i]));
-    }
-    return 0;
+    if (!chip_size && pf_batch_face_masks_shape(b, rows, &F, &H, &W)) return 1;      // refuses like the walker, under this call's name
+    return batch_lanes(b, "pf_batch_face_masks", "face rows", rows, true, [&](pf_handle* h, int f0, int r0, int nr) {
+        const size_t m0 = chip_size ? (size_t)r0 * chip_size * chip_size : (size_t)f0 * H * W;      // the lane's first map
+        return pf_face_masks(h, nr, chip_size, labels + m0, owners ? owners + m0 : nullptr, boxes ? boxes + (size_t)r0 * 4 : nullptr,
+                             valid ? valid + r0 : nullptr, out_mem);
+    });
 }
 
 /* pf_face_redact of the lanes, gathered the same way: lane i writes the frames it ran */
@@ -387,23 +384,16 @@ int pf_batch_face_redact(pf_batch* b, int rows, const int* select, int mode, int
     char buf[200];
     if (const char* why = redact_check(mode, label_mask, strength, pad, select, b->attr_top_k, out, buf, sizeof(buf)))
         PF_BFAIL(b, "pf_batch_face_redact: %s", why);
-    if (!align_out_mem_ok(out_mem)) PF_BFAIL(b, "pf_batch_face_redact: bad out_mem %d", out_mem);
-    if (b->attr_frames == 0) PF_BFAIL(b, "pf_batch_face_redact: no pf_batch_run_frames call has left face rows");
-    if (rows < 0 || rows > b->attr_frames * b->attr_top_k)
-        PF_BFAIL(b, "pf_batch_face_redact: %d rows asked, the last call left %d", rows, b->attr_frames * b->attr_top_k);
+    if (!face_out_mem_ok(out_mem)) PF_BFAIL(b, "pf_batch_face_redact: bad out_mem %d", out_mem);
+    // the frame size comes from lane 0 before any lane runs; the refusals under this call's name come first, so they are asked here too
+    if (batch_rows_check(b, "pf_batch_face_redact", "face rows", rows)) return 1;
     if (rows == 0) return 0;
     int F = 0, H = 0, W = 0;
     if (pf_batch_face_masks_shape(b, rows, &F, &H, &W)) return 1;
-    const int L = (int)b->lane.size(), K = b->attr_top_k;
-    const int per = (b->attr_frames + L - 1) / L;
-    for (int i = 0; i < L; ++i) {
-        const int r0 = i * per * K, nr = std::min(rows - r0, std::min(per, b->attr_frames - i * per) * K);
-        if (nr <= 0) break;
-        if (pf_face_redact(b->lane[i], nr, select ? select + r0 : nullptr, mode, label_mask, strength, pad, colour,
-                           out + (size_t)i * per * H * W * 3, valid ? valid + r0 : nullptr, out_mem))
-            PF_BFAIL(b, "lane %d: %s", i, pf_last_error(b->lane[i]));
-    }
-    return 0;
+    return batch_lanes(b, "pf_batch_face_redact", "face rows", rows, true, [&](pf_handle* h, int f0, int r0, int nr) {
+        return pf_face_redact(h, nr, select ? select + r0 : nullptr, mode, label_mask, strength, pad, colour, out + (size_t)f0 * H * W * 3,
+                              valid ? valid + r0 : nullptr, out_mem);
+    });
 }
 
 }  // extern "C"

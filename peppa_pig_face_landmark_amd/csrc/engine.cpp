@@ -37,6 +37,7 @@
 #include "k_align.h"
 #include "k_mask.h"
 #include "k_redact.h"
+#include "face_rows.h"
 #include "pf_program.h"
 
 
@@ -119,19 +120,13 @@ struct pf_handle {
     void* comm = nullptr;
     unsigned char comm_id[128] = {0};
     int comm_rank = -1, comm_world = 0;
-    // rows of face-attribute records the last landmark-running call left (pf_face_attrs): kind 0 = none, 1 = rows 0 .. attr_rows-1 of
-    // the landmark program's out_buf2 as they are (pf_landmark_forward, pf_run_frames*), 2 = the same with the valid flags of
-    // pf_landmarks (snapshot in h_attr_valid / d_attr_valid, taken by that call), 3 = rows of attr_src (the tracking calls: records
-    // compacted like their scores by track_group_kernel into d_track_attrs)
-    int attr_kind = 0, attr_rows = 0;
-    const float* attr_src = nullptr;
-    std::vector<int> h_attr_valid;
-    int* d_attr_valid = nullptr; size_t attr_valid_bytes = 0;
-    float* d_track_attrs = nullptr; size_t track_attrs_bytes = 0;
-    // aligned face chips (align.inl): scratch, and where the last pipeline call left frames / landmarks / live flags (pf_face_chips)
-    AlignState align;
-    // face-region label maps (mask.inl): scratch; what the last call left is read from `align`
-    MaskState mask;
+    // what the handle's last call left for the stages behind the landmarks (face_rows.h): the rows with their frames, landmarks and
+    // live flags (pf_face_chips, pf_face_masks*, pf_face_redact) and the attribute rows (pf_face_attrs); written by its own functions only
+    FaceRows last;
+    float* d_track_attrs = nullptr; size_t track_attrs_bytes = 0;      // attribute records of the tracking calls (FaceRows::attr_src)
+    StageUpload upload;      // host frames / landmarks / counts of pf_align_faces, pf_mask_faces, pf_redact_faces (stage_faces, face_rows.inl)
+    AlignState align;        // aligned face chips (align.inl): scratch of its two kernels
+    MaskState mask;          // face-region label maps (mask.inl): scratch of its two kernels
     // face redaction (redact.inl): the label maps it reads and the staging of host outputs
     RedactState redact;
     // profiling
@@ -501,11 +496,12 @@ void pf_destroy(pf_handle* h) {
         if (p.d_range) (void)hipFree(p.d_range);
     }
     if (h->d_stage) (void)hipFree(h->d_stage);
-    if (h->d_attr_valid) (void)hipFree(h->d_attr_valid);
     if (h->d_track_attrs) (void)hipFree(h->d_track_attrs);
     if (h->d_dbg) { print_cycle_counters(h); (void)hipFree(h->d_dbg); }
     if (h->h_status) (void)hipHostFree(h->h_status);
     h->pipe.release();
+    h->last.release();
+    h->upload.release();
     h->align.release();
     h->mask.release();
     h->redact.release();
@@ -529,7 +525,7 @@ int pf_sync(pf_handle* h) {
 int pf_load_program(pf_handle* h, int slot, const void* blob, size_t bytes, int max_batch) {
     if (!h) return 1;
     if (slot < 0 || slot >= PF_NET_SLOTS) PF_FAIL(h, "slot %d out of range", slot);
-    if (slot == PF_NET_LANDMARK) { h->attr_kind = 0; h->align.kind = 0; }      // the records of the previous program are gone with its arena
+    if (slot == PF_NET_LANDMARK) h->last.forget();      // the records of the previous program are gone with its arena
     if (!blob || bytes < sizeof(PfHeader)) PF_FAIL(h, "program blob too small");
     if (max_batch < 1) PF_FAIL(h, "max_batch must be >= 1");
     PF_HIP(h, hipSetDevice(h->device));
@@ -616,10 +612,9 @@ int pf_landmark_forward(pf_handle* h, const void* input, int input_kind, int mem
     h->pipe.d_crop_for_decode = nullptr;
     h->pipe.d_kps_for_decode = nullptr;
     begin_call(h);
-    h->attr_kind = 0;
-    h->align.kind = 2;            // rows without a frame (pf_face_chips)
+    h->last.note_frameless();     // rows without a frame (pf_face_chips)
     if (net_forward_common(h, PF_NET_LANDMARK, input, input_kind, mem, batch, input_kind == PF_INPUT_U8_NHWC ? px : px * 4)) return 1;
-    h->attr_kind = 1; h->attr_rows = batch;
+    h->last.note_attrs(1, batch);
     if (copy_out(h, p.buf_ptr(p.hdr.out_buf0), loc_fix, (size_t)batch * p.buf_item_bytes(p.hdr.out_buf0), out_mem)) return 1;
     if (copy_out(h, p.buf_ptr(p.hdr.out_buf1), score, (size_t)batch * p.buf_item_bytes(p.hdr.out_buf1), out_mem)) return 1;
     if (out_mem == PF_MEM_HOST) {
@@ -652,15 +647,16 @@ int pf_face_attrs(pf_handle* h, int rows, float* out, int raw, int out_mem) {
         PF_FAIL(h, "pf_face_attrs: the loaded landmark program has no face-attribute head (build it with face_attrs=True)");
     if (!out || rows < 0 || (out_mem != PF_MEM_HOST && out_mem != PF_MEM_DEVICE && out_mem != PF_MEM_HOST_PINNED))
         PF_FAIL(h, "pf_face_attrs: bad arguments");
-    if (h->attr_kind == 0) PF_FAIL(h, "pf_face_attrs: the handle's last call left no face-attribute rows (pf_landmark_forward, "
-                                      "pf_landmarks*, pf_run_frames*, pf_track_frame* and pf_track_streams do)");
-    if (rows > h->attr_rows) PF_FAIL(h, "pf_face_attrs: %d rows asked, the last call left %d", rows, h->attr_rows);
+    const FaceRows& s = h->last;        // its attribute half
+    if (s.attr_kind == 0) PF_FAIL(h, "pf_face_attrs: the handle's last call left no face-attribute rows (pf_landmark_forward, "
+                                     "pf_landmarks*, pf_run_frames*, pf_track_frame* and pf_track_streams do)");
+    if (rows > s.attr_rows) PF_FAIL(h, "pf_face_attrs: %d rows asked, the last call left %d", rows, s.attr_rows);
     if (rows == 0) return 0;
     PF_HIP(h, hipSetDevice(h->device));
     FaceAttrsPickArgs a{};
-    a.rec = h->attr_kind == 3 ? h->attr_src : (const float*)p.buf_ptr(p.hdr.out_buf2);
+    a.rec = s.attr_kind == 3 ? s.attr_src : (const float*)p.buf_ptr(p.hdr.out_buf2);
     a.col0 = raw ? PF_FACE_ATTR_RAW : PF_FACE_ATTR_COOKED;
-    a.valid = h->attr_kind == 2 ? h->d_attr_valid : nullptr; a.rows = rows;
+    a.valid = s.attr_kind == 2 ? s.d_attr_valid : nullptr; a.rows = rows;
     if (out_mem == PF_MEM_DEVICE) {
         a.out = out;
         PF_LAUNCH(face_attrs_pick_kernel, dim3(pf_div_up(rows * 7, 256)), dim3(256), h->stream, a);
@@ -673,7 +669,7 @@ int pf_face_attrs(pf_handle* h, int rows, float* out, int raw, int out_mem) {
     PF_HIP(h, hipMemcpyAsync(rec.data(), a.rec, rec.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     PF_HIP(h, hipStreamSynchronize(h->stream));
     for (int i = 0; i < rows; ++i) {
-        if (h->attr_kind == 2 && !h->h_attr_valid[i]) continue;
+        if (s.attr_kind == 2 && !s.h_attr_valid[i]) continue;
         memcpy(out + (size_t)i * 7, rec.data() + (size_t)i * PF_FACE_ATTR_REC + a.col0, 7 * sizeof(float));
     }
     return 0;
@@ -753,6 +749,7 @@ int pf_profile_fetch(pf_handle* h, char* names, size_t names_cap, float* ms, int
 
 }  // extern "C"
 
+#include "face_rows.inl"
 #include "align.inl"
 #include "mask.inl"
 #include "redact.inl"

@@ -23,12 +23,8 @@ struct AlignFrame {
     int H, W, row_stride, pad_;
 };
 
-// Host side of a handle: scratch of the two kernels, and what the handle's last pipeline call left on the device for pf_face_chips
-// (next to pf_handle::attr_kind): rows, where their landmarks, live flags and frames are.
+// Host side of a handle: scratch of the two kernels (what the handle's last call left for pf_face_chips is FaceRows, face_rows.h)
 struct AlignState {
-    unsigned char* d_frames = nullptr; size_t frames_bytes = 0;      // host frames / landmarks / counts of pf_align_faces
-    char* d_kps = nullptr; size_t kps_bytes = 0;
-    int* d_counts = nullptr; size_t counts_bytes = 0;
     AlignFrame* d_table = nullptr; size_t table_bytes = 0;
     std::vector<AlignFrame> h_table;
     double* d_rec = nullptr; size_t rec_bytes = 0;
@@ -37,14 +33,8 @@ struct AlignState {
     double* d_mats = nullptr; size_t mats_bytes = 0;
     std::vector<int> h_valid;
     int lds_budget = PF_ALIGN_LDS_BYTES;
-    // kind 0 = the last call left no rows, 1 = rows 0 .. rows-1, row r in frame r / per_frame, 2 = rows without a frame (pf_landmark_forward)
-    int kind = 0, rows = 0, per_frame = 1, kps_f64 = 0, valid_stride = 0;
-    const void* kps = nullptr;
-    const int* counts = nullptr;
-    const int* valid = nullptr;
-    std::vector<AlignFrame> frames;
     void release() {
-        void* ptrs[] = {d_frames, d_kps, d_counts, d_table, d_rec, d_valid, d_chips, d_mats};
+        void* ptrs[] = {d_table, d_rec, d_valid, d_chips, d_mats};
         for (void* p : ptrs) if (p) (void)hipFree(p);
         *this = AlignState();
     }

@@ -1,6 +1,6 @@
 // Face-region label maps (included after align.inl; kernels in k_mask.h):
-//   pf_mask_faces         stage-level: the caller supplies landmarks and the frame's size
-//   pf_face_masks         the faces of the handle's last pipeline call, from the record chips_note_* keeps for pf_face_chips
+//   pf_mask_faces         stage-level: the caller supplies landmarks and the frame's size (prologue: stage_faces without frames)
+//   pf_face_masks         the faces of the handle's last pipeline call, from the record it left (pf_handle::last, face_rows.h)
 //   pf_batch_face_masks   the same over the lanes of a pf_batch (batch.inl)
 // A mask reads the landmarks and the frame's size, never a pixel.
 namespace {
@@ -18,12 +18,12 @@ int mask_run(pf_handle* h, int rows, int per_frame, int H, int W, int S, const v
     const size_t map_bytes = (size_t)mh * mw;
     const int tiles_x = pf_div_up(mw, PF_MASK_TW), tiles = tiles_x * pf_div_up(mh, PF_MASK_TH);
     if ((long long)tiles * images > 0x7fffffffLL) PF_FAIL(h, "pf_mask_faces: %d maps of %d x %d are too many", images, mh, mw);
-    if (align_ensure(h, s.d_rec, s.rec_bytes, (size_t)rows * PF_MASK_REC * sizeof(int))) return 1;
+    if (scratch_ensure(h, s.d_rec, s.rec_bytes, (size_t)rows * PF_MASK_REC * sizeof(int))) return 1;
     if (!to_device) {
-        if (align_ensure(h, s.d_labels, s.labels_bytes, (size_t)images * map_bytes)) return 1;
-        if (owners && align_ensure(h, s.d_owners, s.owners_bytes, (size_t)images * map_bytes)) return 1;
-        if (boxes && align_ensure(h, s.d_boxes, s.boxes_bytes, (size_t)rows * 4 * sizeof(int))) return 1;
-        if (align_ensure(h, s.d_valid, s.valid_bytes, (size_t)rows * sizeof(int))) return 1;
+        if (scratch_ensure(h, s.d_labels, s.labels_bytes, (size_t)images * map_bytes)) return 1;
+        if (owners && scratch_ensure(h, s.d_owners, s.owners_bytes, (size_t)images * map_bytes)) return 1;
+        if (boxes && scratch_ensure(h, s.d_boxes, s.boxes_bytes, (size_t)rows * 4 * sizeof(int))) return 1;
+        if (scratch_ensure(h, s.d_valid, s.valid_bytes, (size_t)rows * sizeof(int))) return 1;
     }
     MaskEdgesArgs ea{};
     ea.kps = d_kps; ea.kps_f64 = kps_f64; ea.n = rows; ea.per_frame = per_frame; ea.S = S; ea.H = mh; ea.W = mw;
@@ -54,19 +54,9 @@ int mask_run(pf_handle* h, int rows, int per_frame, int H, int W, int S, const v
         if (owners) PF_HIP(h, hipMemcpyAsync(owners, s.d_owners, (size_t)images * map_bytes, hipMemcpyDeviceToHost, h->stream));
     }
     PF_HIP(h, hipStreamSynchronize(h->stream));
-    if (S || boxes) {
-        for (int r = 0; r < rows;) {       // runs of valid rows come over in one copy each
-            if (!s.h_valid[r]) { ++r; continue; }
-            int e = r + 1;
-            while (e < rows && s.h_valid[e]) ++e;
-            if (S) PF_HIP(h, hipMemcpyAsync(labels + (size_t)r * map_bytes, s.d_labels + (size_t)r * map_bytes, (size_t)(e - r) * map_bytes,
-                                            hipMemcpyDeviceToHost, h->stream));
-            if (boxes) PF_HIP(h, hipMemcpyAsync(boxes + (size_t)r * 4, s.d_boxes + (size_t)r * 4, (size_t)(e - r) * 4 * sizeof(int),
-                                                hipMemcpyDeviceToHost, h->stream));
-            r = e;
-        }
-        PF_HIP(h, hipStreamSynchronize(h->stream));
-    }
+    if ((S || boxes) && copy_valid_runs(h, s.h_valid, rows, RowCopy{S ? labels : nullptr, s.d_labels, map_bytes},
+                                        RowCopy{boxes, s.d_boxes, 4 * sizeof(int)}))
+        return 1;
     if (valid) memcpy(valid, s.h_valid.data(), (size_t)rows * sizeof(int));
     return 0;
 }
@@ -83,16 +73,8 @@ const char* mask_check(int chip_size, int per_frame, const void* owners, const v
     return nullptr;
 }
 
-// the record of the last pipeline call, as pf_face_chips judges it; on success the frame size the maps take
-int mask_last_call(pf_handle* h, const char* who, int rows, int* H, int* W) {
-    const AlignState& s = h->align;
-    if (s.kind == 2) PF_FAIL(h, "%s: the handle's last call was pf_landmark_forward, which has no frame to lay the maps over", who);
-    if (s.kind == 0)
-        PF_FAIL(h, "%s: the handle's last call left no face rows (pf_landmarks*, pf_run_frames*, pf_track_frame* and pf_track_streams do)", who);
-    if (rows > s.rows) PF_FAIL(h, "%s: %d rows asked, the last call left %d", who, rows, s.rows);
-    *H = s.frames[0].H; *W = s.frames[0].W;
-    return 0;
-}
+// last_face_rows for an accessor that lays maps over the frames of the last call (their size: frames[0].H x frames[0].W)
+const char* const kNoFrameForMaps = "no frame to lay the maps over";
 
 }  // namespace
 
@@ -103,49 +85,35 @@ int pf_mask_faces(pf_handle* h, int n_frames, int height, int width, const void*
     if (!h) return 1;
     char buf[160];
     if (const char* why = mask_check(chip_size, top_k, owners, boxes, buf, sizeof(buf))) PF_FAIL(h, "pf_mask_faces: %s", why);
-    if (n_frames < 1 || top_k < 1 || !kps || !labels || (kps_mem != PF_MEM_HOST && kps_mem != PF_MEM_DEVICE) || !align_out_mem_ok(out_mem) ||
-        (chip_size == 0 && (height < 1 || width < 1 || height > 32768 || width > 32768)))
-        PF_FAIL(h, "pf_mask_faces: bad arguments");
-    if ((long long)n_frames * top_k > (1 << 20)) PF_FAIL(h, "pf_mask_faces: %d x %d face slots are too many", n_frames, top_k);
-    PF_HIP(h, hipSetDevice(h->device));
-    AlignState& s = h->align;       // the upload scratch of pf_align_faces serves here too
-    const int rows = n_frames * top_k;
-    const void* d_kps = kps;
-    const int* d_counts = counts;
-    if (kps_mem == PF_MEM_HOST) {
-        const size_t kb = (size_t)rows * 196 * (kps_f64 ? sizeof(double) : sizeof(float));
-        if (align_ensure(h, s.d_kps, s.kps_bytes, kb)) return 1;
-        PF_HIP(h, hipMemcpyAsync(s.d_kps, kps, kb, hipMemcpyHostToDevice, h->stream));
-        d_kps = s.d_kps;
-        if (counts) {
-            if (align_ensure(h, s.d_counts, s.counts_bytes, (size_t)n_frames * sizeof(int))) return 1;
-            PF_HIP(h, hipMemcpyAsync(s.d_counts, counts, (size_t)n_frames * sizeof(int), hipMemcpyHostToDevice, h->stream));
-            d_counts = s.d_counts;
-        }
-    }
-    return mask_run(h, rows, top_k, height, width, chip_size, d_kps, kps_f64 ? 1 : 0, d_counts, nullptr, 0, labels, owners, boxes, valid, out_mem);
+    // the frame's size matters in frame space only; the same refusal as the shared checks of stage_faces, which looks at neither
+    if (chip_size == 0 && (height < 1 || width < 1 || height > 32768 || width > 32768)) PF_FAIL(h, "pf_mask_faces: bad arguments");
+    StageFaces st;
+    if (stage_faces(h, "pf_mask_faces", false, nullptr, 0, n_frames, height, width, kps, kps_f64, kps_mem, counts, top_k, labels, out_mem, &st)) return 1;
+    return mask_run(h, st.rows, top_k, height, width, chip_size, st.d_kps, kps_f64 ? 1 : 0, st.d_counts, nullptr, 0, labels, owners, boxes, valid,
+                    out_mem);
 }
 
 int pf_face_masks(pf_handle* h, int rows, int chip_size, uint8_t* labels, uint8_t* owners, int* boxes, int* valid, int out_mem) {
     if (!h) return 1;
     char buf[160];
-    if (const char* why = mask_check(chip_size, h->align.kind == 1 ? h->align.per_frame : 0, owners, boxes, buf, sizeof(buf)))
+    if (const char* why = mask_check(chip_size, h->last.kind == 1 ? h->last.per_frame : 0, owners, boxes, buf, sizeof(buf)))
         PF_FAIL(h, "pf_face_masks: %s", why);
-    if (!labels || rows < 0 || !align_out_mem_ok(out_mem)) PF_FAIL(h, "pf_face_masks: bad arguments");
-    int H = 0, W = 0;
-    if (mask_last_call(h, "pf_face_masks", rows, &H, &W)) return 1;
+    if (!labels || rows < 0 || !face_out_mem_ok(out_mem)) PF_FAIL(h, "pf_face_masks: bad arguments");
+    const FaceRows* s = nullptr;
+    if (last_face_rows(h, "pf_face_masks", kNoFrameForMaps, rows, &s)) return 1;
     if (rows == 0) return 0;
     PF_HIP(h, hipSetDevice(h->device));
-    const AlignState& s = h->align;
-    return mask_run(h, rows, s.per_frame, H, W, chip_size, s.kps, s.kps_f64, s.counts, s.valid, s.valid_stride, labels, owners, boxes, valid,
-                    out_mem);
+    return mask_run(h, rows, s->per_frame, s->frames[0].H, s->frames[0].W, chip_size, s->kps, s->kps_f64, s->counts, s->valid, s->valid_stride,
+                    labels, owners, boxes, valid, out_mem);
 }
 
 int pf_face_masks_shape(pf_handle* h, int rows, int* n_frames, int* height, int* width) {
     if (!h) return 1;
     if (rows < 0 || !n_frames || !height || !width) PF_FAIL(h, "pf_face_masks_shape: bad arguments");
-    if (mask_last_call(h, "pf_face_masks_shape", rows, height, width)) return 1;
-    *n_frames = pf_div_up(rows, h->align.per_frame);
+    const FaceRows* s = nullptr;
+    if (last_face_rows(h, "pf_face_masks_shape", kNoFrameForMaps, rows, &s)) return 1;
+    *n_frames = pf_div_up(rows, s->per_frame);
+    *height = s->frames[0].H; *width = s->frames[0].W;
     return 0;
 }
 

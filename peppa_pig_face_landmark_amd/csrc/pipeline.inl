@@ -32,7 +32,7 @@ int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
 int ensure_pipeline(pf_handle* h, int frames, int faces, int top_k, int rows) {
     PipelineScratch& s = h->pipe;
-    if (frames > s.cap_frames || top_k > s.cap_topk || rows > s.cap_rows || faces > s.cap_faces) h->align.kind = 0;   // pf_face_chips reads d_sel_count / d_kps / d_crop_params
+    if (frames > s.cap_frames || top_k > s.cap_topk || rows > s.cap_rows || faces > s.cap_faces) h->last.forget_frames();   // pf_face_chips reads d_sel_count / d_kps / d_crop_params
     if (frames > s.cap_frames || top_k > s.cap_topk || rows > s.cap_rows) {
         const int F = std::max(frames, s.cap_frames), K = std::max(top_k, s.cap_topk), R = std::max(rows, s.cap_rows);
         const int cap = next_pow2(std::max(R, 2));
@@ -82,7 +82,7 @@ int stage_frames(pf_handle* h, const uint8_t* frames, int mem, size_t bytes, con
         *d_out = h->pipe.d_cur;
         return 0;
     }
-    h->align.kind = 0;      // the staged frames of the last call, which pf_face_chips would read, are overwritten
+    h->last.forget_frames();      // the staged frames of the last call, which pf_face_chips would read, are overwritten
     if (ensure_dev(h, h->pipe.d_frames, h->pipe.frames_bytes, bytes)) return 1;
     PF_HIP(h, hipMemcpyAsync(h->pipe.d_frames, frames, bytes, hipMemcpyHostToDevice, h->stream));
     *d_out = h->pipe.d_frames;
@@ -225,7 +225,7 @@ static int landmarks_impl(pf_handle* h, const uint8_t* bgr, int mem, int height,
     Program& lm = h->prog[PF_NET_LANDMARK];
     if (!lm.loaded) PF_FAIL(h, "landmark program not loaded");
     if (n < 0 || (!bgr && mem != PF_MEM_RESIDENT) || height < 1 || width < 1 || row_stride < width * 3) PF_FAIL(h, "pf_landmarks: bad arguments");
-    h->align.kind = 0;          // a call without boxes leaves no rows for pf_face_chips either
+    h->last.forget_frames();    // a call without boxes leaves no rows for pf_face_chips either
     if (n == 0) return 0;
     PF_HIP(h, hipSetDevice(h->device));
     if (ensure_pipeline(h, 1, n, n, 2)) return 1;
@@ -240,7 +240,7 @@ static int landmarks_impl(pf_handle* h, const uint8_t* bgr, int mem, int height,
         PF_HIP(h, hipMemcpyAsync(h->pipe.d_sel_boxes, boxes, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice, h->stream));
     }
     begin_call(h);
-    h->attr_kind = 0;
+    h->last.forget();
     if (run_landmark_stage(h, d_frames, height, width, row_stride, h->pipe.d_sel_boxes, nullptr, n, n, d_b64)) return 1;
     std::vector<int> params((size_t)n * 8);
     std::vector<float> hk((size_t)n * kNumPoints * 2), hs((size_t)n * kNumPoints);
@@ -249,12 +249,8 @@ static int landmarks_impl(pf_handle* h, const uint8_t* bgr, int mem, int height,
     PF_HIP(h, hipMemcpyAsync(hs.data(), lm.buf_ptr(lm.hdr.out_buf1), hs.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     PF_HIP(h, hipStreamSynchronize(h->stream));
     if (check_numerics(h)) return 1;
-    if (lm.hdr.out_buf2 >= 0) {       // pf_face_attrs: the valid flags of THIS call, kept apart from the crop-parameter scratch
-        h->h_attr_valid.resize(n);
-        for (int i = 0; i < n; ++i) h->h_attr_valid[i] = params[(size_t)i * 8] != 0;
-        if (ensure_dev(h, h->d_attr_valid, h->attr_valid_bytes, (size_t)n * sizeof(int))) return 1;
-        PF_HIP(h, hipMemcpy(h->d_attr_valid, h->h_attr_valid.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-    }
+    // pf_face_attrs: the valid flags of THIS call, kept apart from the crop-parameter scratch
+    if (lm.hdr.out_buf2 >= 0 && face_rows_snapshot_valid(h, params.data(), 8, n)) return 1;
     for (int i = 0; i < n; ++i) {
         const int ok = params[(size_t)i * 8];
         if (valid) valid[i] = ok;
@@ -262,9 +258,9 @@ static int landmarks_impl(pf_handle* h, const uint8_t* bgr, int mem, int height,
         if (kps) memcpy(kps + (size_t)i * kNumPoints * 2, hk.data() + (size_t)i * kNumPoints * 2, kNumPoints * 2 * sizeof(float));
         if (scores) memcpy(scores + (size_t)i * kNumPoints, hs.data() + (size_t)i * kNumPoints, kNumPoints * sizeof(float));
     }
-    if (lm.hdr.out_buf2 >= 0) { h->attr_kind = 2; h->attr_rows = n; }
+    if (lm.hdr.out_buf2 >= 0) h->last.note_attrs(2, n);
     // pf_face_chips: box order, the valid flags are the first word of each row's crop parameters
-    chips_note_frames(h, d_frames, 0, 1, height, width, row_stride, n, n, h->pipe.d_kps, 0, nullptr, h->pipe.d_crop_params, 8);
+    h->last.note_frames(face_frames(d_frames, 0, 1, height, width, row_stride), n, n, h->pipe.d_kps, 0, nullptr, h->pipe.d_crop_params, 8);
     return 0;
 }
 
@@ -346,8 +342,7 @@ int pf_run_frames_planted(pf_handle* h, const uint8_t* frames, int mem, int n_fr
     if (out_mem != PF_MEM_HOST && out_mem != PF_MEM_DEVICE && out_mem != PF_MEM_HOST_PINNED) PF_FAIL(h, "pf_run_frames: bad out_mem %d", out_mem);
     // results into page-locked host memory are plain asynchronous copies on the stream: they capture into the graph too
     begin_call(h);
-    h->attr_kind = 0;
-    h->align.kind = 0;
+    h->last.forget();
     const bool capturable = !h->profiling && mem == PF_MEM_DEVICE && (out_mem == PF_MEM_DEVICE || out_mem == PF_MEM_HOST_PINNED);
     const GraphKey key = GraphKey::whole_call(frames, det_rows, n_frames, height, width, rows, score_thres, iou_thres, min_face, top_k,
                                               counts, boxes, kps, scores, out_mem);
@@ -359,12 +354,12 @@ int pf_run_frames_planted(pf_handle* h, const uint8_t* frames, int mem, int n_fr
         PF_HIP(h, hipStreamSynchronize(h->stream));
         if (check_numerics(h)) return 1;
     }
-    h->attr_kind = 1; h->attr_rows = n_frames * top_k;          // rows [F][top_k], like kps (pf_face_attrs)
+    h->last.note_attrs(1, n_frames * top_k);          // rows [F][top_k], like kps (pf_face_attrs)
     // pf_face_chips: the frames where stage_frames found or put them (a replayed graph does not run it again)
     const int fmem = mem & 0xff;
     const unsigned char* d_left = fmem == PF_MEM_DEVICE ? frames : (fmem == PF_MEM_RESIDENT ? h->pipe.d_cur : h->pipe.d_frames);
-    chips_note_frames(h, d_left, (size_t)height * width * 3, n_frames, height, width, width * 3, n_frames * top_k, top_k, h->pipe.d_kps, 0,
-                      h->pipe.d_sel_count);
+    h->last.note_frames(face_frames(d_left, (size_t)height * width * 3, n_frames, height, width, width * 3), n_frames * top_k, top_k,
+                        h->pipe.d_kps, 0, h->pipe.d_sel_count);
     return 0;
 }
 
@@ -411,7 +406,7 @@ int pf_set_frame(pf_handle* h, const uint8_t* bgr, int mem, int height, int widt
     PF_HIP(h, hipSetDevice(h->device));
     PipelineScratch& s = h->pipe;
     const size_t bytes = (size_t)height * row_stride;
-    h->align.kind = 0;      // pf_face_chips: the resident frame the last call's rows belong to is replaced
+    h->last.forget_frames();      // pf_face_chips: the resident frame the last call's rows belong to is replaced
     // rotate: the current resident frame becomes the previous one
     std::swap(s.d_cur, s.d_prev);
     std::swap(s.cur_bytes, s.prev_bytes);
@@ -529,7 +524,7 @@ static int crop_faces_impl(pf_handle* h, const uint8_t* bgr, int mem, int height
     if (!bgr || n < 1 || out_size < 1 || height < 1 || width < 1 || row_stride < width * 3) PF_FAIL(h, "pf_crop_faces: bad arguments");
     PF_HIP(h, hipSetDevice(h->device));
     if (ensure_pipeline(h, 1, n, n, 2)) return 1;
-    h->align.kind = 0;          // the crop parameters (and maybe the staged frame) of the last landmark call are overwritten
+    h->last.forget_frames();    // the crop parameters (and maybe the staged frame) of the last landmark call are overwritten
     const unsigned char* d_frames = nullptr;
     if (stage_frames(h, bgr, mem, (size_t)height * row_stride, &d_frames)) return 1;
     const double* d_b64 = nullptr;

@@ -179,8 +179,7 @@ static int track_frame_impl(pf_handle* h, const uint8_t* bgr, int mem, int heigh
                             float track_iou_thres, float smooth_box, float diff_thres,
                             int* n_out, double* boxes, double* kps, float* scores, int* detector_ran) {
     if (!h) return 1;
-    h->attr_kind = 0;
-    h->align.kind = 0;
+    h->last.forget();
     Program& det = h->prog[PF_NET_DETECTOR];
     Program& lm = h->prog[PF_NET_LANDMARK];
     if (!det.loaded || !lm.loaded) PF_FAIL(h, "pf_track_frame: detector and landmark programs must be loaded");
@@ -228,9 +227,9 @@ static int track_frame_impl(pf_handle* h, const uint8_t* bgr, int mem, int heigh
     }
     n = std::min(n, top_k);
     *n_out = n;
-    if (lm.hdr.out_buf2 >= 0) { h->attr_kind = 3; h->attr_src = h->d_track_attrs; h->attr_rows = n; }   // rows [n], like kps
+    if (lm.hdr.out_buf2 >= 0) h->last.note_attrs(3, n, h->d_track_attrs);   // rows [n], like kps
     // pf_face_chips: the n compacted faces, their smoothed float64 landmarks, the resident frame
-    chips_note_frames(h, h->pipe.d_cur, 0, 1, height, width, width * 3, n, top_k, P.v.out_lm, 1, nullptr);
+    h->last.note_frames(face_frames(h->pipe.d_cur, 0, 1, height, width, width * 3), n, top_k, P.v.out_lm, 1, nullptr);
     if (n > 0) {
         if (boxes) memcpy(boxes, hb.data(), (size_t)n * 4 * sizeof(double));
         if (kps) memcpy(kps, hk.data(), (size_t)n * 196 * sizeof(double));
@@ -246,7 +245,7 @@ int pf_track_streams_config(pf_handle* h, int max_streams, int top_k) {
     if (max_streams < 1 || top_k < 1) PF_FAIL(h, "pf_track_streams_config: bad arguments (max_streams %d, top_k %d)", max_streams, top_k);
     PF_HIP(h, hipSetDevice(h->device));
     TrackPool& P = h->streams;
-    h->align.kind = 0;
+    h->last.forget_frames();      // the pool's frame slots and landmarks, which the rows of a pf_track_streams call point at, are replaced
     if (track_pool_alloc(h, P, max_streams, top_k)) return 1;
     PF_HIP(h, hipMalloc((void**)&P.d_sums, (size_t)max_streams * sizeof(unsigned long long)));
     PF_HIP(h, hipMalloc((void**)&P.d_det_idx, (size_t)max_streams * sizeof(int)));
@@ -270,8 +269,7 @@ int pf_track_streams(pf_handle* h, int n, const int* stream_ids, const uint8_t* 
                      float track_iou_thres, float smooth_box, float diff_thres,
                      int* counts, double* boxes, double* kps, float* scores, int* detector_ran) {
     if (!h) return 1;
-    h->attr_kind = 0;
-    h->align.kind = 0;
+    h->last.forget();
     TrackPool& P = h->streams;
     // every check before anything changes: a rejected call leaves every stream as it was
     if (P.S == 0) PF_FAIL(h, "pf_track_streams: no stream pool (call pf_track_streams_config first)");
@@ -356,10 +354,11 @@ int pf_track_streams(pf_handle* h, int n, const int* stream_ids, const uint8_t* 
         h->err = why;
         return 1;
     }
-    if (lm.hdr.out_buf2 >= 0) { h->attr_kind = 3; h->attr_src = h->d_track_attrs; h->attr_rows = n * K; }   // rows [n][K], like kps
+    if (lm.hdr.out_buf2 >= 0) h->last.note_attrs(3, n * K, h->d_track_attrs);   // rows [n][K], like kps
     // pf_face_chips: rows [n][K]; frame i is read from its stream's slot, where the gate stored it
-    chips_note_frames(h, P.d_frames, 0, n, height, width, width * 3, n * K, K, P.v.out_lm, 1, P.v.out_count);
-    for (int i = 0; i < n; ++i) h->align.frames[i].base = P.d_frames + (size_t)stream_ids[i] * P.frame_slot_bytes;
+    std::vector<AlignFrame> slots(n);
+    for (int i = 0; i < n; ++i) slots[i] = AlignFrame{P.d_frames + (size_t)stream_ids[i] * P.frame_slot_bytes, height, width, width * 3, 0};
+    h->last.note_frames(std::move(slots), n * K, K, P.v.out_lm, 1, P.v.out_count);
     return 0;
 }
 

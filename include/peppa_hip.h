@@ -297,6 +297,55 @@ int pf_decode_jpeg(pf_handle* h, const uint8_t* jpeg, size_t bytes, int* height,
 int pf_decode_jpeg_batch(pf_handle* h, int n, const uint8_t* const* jpegs, const size_t* sizes, int threads, int* height,
                          int* width, const uint8_t** d_frames);
 
+/* The forward direction: n packed BGR images of one size -> n complete baseline JFIF files, written by device kernels
+ * (csrc/k_jpeg_enc.h).  Every byte is what libjpeg(-turbo) writes for the same quality and sampling without its optimisation
+ * pass and with one restart interval per MCU row (Pillow: save(quality=q, subsampling=s, restart_marker_rows=1)); the numpy
+ * restatement is tests/jpeg_enc_ref.py, the prose INTEGRATION.md 4g.  Integers throughout:
+ *   colour     F(x) = int(x 65536 + .5): Y = (F(.299) R + F(.587) G + F(.114) B + 32768) >> 16,
+ *              Cb = (-F(.16874) R - F(.33126) G + F(.5) B + (128 << 16) + 32767) >> 16,
+ *              Cr = (F(.5) R - F(.41869) G - F(.08131) B + (128 << 16) + 32767) >> 16 (arithmetic shifts; byte 0 of a pixel is B)
+ *   planes     luma is sampled 1x1 (444), 2x1 (422) or 2x2 (420) against chroma.  The converted plane repeats its last column and
+ *              its last row up to the component's blocks; chroma is then averaged, 2x2: (a + b + c + d + bias) >> 2 with bias
+ *              1, 2, 1, 2 .. along the output columns, 2x1: (a + b + bias) >> 1 with bias 0, 1, 0, 1 ..; then the last down-sampled
+ *              row repeats to a multiple of 8 rows
+ *   DCT        libjpeg's "islow" forward DCT on sample - 128 (13-bit constants, row pass scaled by 4, column pass descaled), the
+ *              forward twin of the decoder's
+ *   quantiser  ITU T.81 K.1 / K.2 scaled as libjpeg scales them (s = 5000 / q below 50, else 200 - 2 q; (base s + 50) / 100 clamped
+ *              to 1 .. 255); with d = 8 Q the coefficient is sign(c) ((|c| + (d >> 1)) / d)
+ *   blocks     a luma block an MCU needs beyond the image's blocks has no AC and the DC of the block coded before it in the MCU
+ *   entropy    one interleaved scan (ids 1, 2, 3), the standard Huffman tables K.3 - K.6, restart interval = one MCU row: at its
+ *              end the bits are padded with ones, RSTm follows (m counts modulo 8; EOI behind the last), DC predictions return to 0
+ *   file       SOI, APP0 (JFIF 1.1, density 1 x 1), DQT 0, DQT 1, SOF0, DHT DC0, AC0, DC1, AC1, DRI, SOS, the scan, EOI
+ * So the rows of MCUs are independent on the device, and pf_decode_jpeg* takes the files on its restart-interval path.
+ *
+ * Image i starts at images + i * height * row_stride, row_stride >= 3 * width with any alignment; mem = PF_MEM_HOST, PF_MEM_DEVICE
+ * or PF_MEM_RESIDENT (then n = 1 and images may be NULL).  quality 1 .. 100, subsampling 444, 422 or 420 (the values pf_jpeg_info
+ * reports), height and width 1 .. 65535.  File i goes to out + i * capacity and sizes[i] is its length.  A file that does not fit
+ * its slot leaves sizes[i] = -(bytes needed); the call still succeeds, the content of that slot is unspecified, no byte outside the
+ * slot is touched and no other image is affected.  Where it fits, exactly sizes[i] bytes are written and the rest of the slot is
+ * untouched.  out_mem = PF_MEM_DEVICE: out and sizes are device memory and everything is enqueued on the handle's stream without
+ * a read-back; PF_MEM_HOST: the files are copied and the call synchronises.  The call is never captured into a graph and leaves the
+ * record of the handle's last call alone, so pf_face_chips / pf_face_redact (out_mem = PF_MEM_DEVICE) followed by pf_encode_jpeg
+ * (mem = PF_MEM_DEVICE) on the same handle compose without a synchronisation.
+ *
+ * Scratch (coefficients: 128 bytes per block; the bit stream at its longest: about 208 bytes per block; the intervals' lengths)
+ * belongs to the handle.  Calls run in internal chunks of images whose scratch stays below PF_JPEG_ENC_SCRATCH = 256 MiB, except that
+ * one image always runs whole (4:2:0: about 8 bytes per pixel, 4:4:4: about 16).  Images whose pf_encode_jpeg_bound exceeds 2^31 - 1
+ * (about 220 megapixels in 4:2:0, 110 in 4:4:4) are refused.
+ *
+ * pf_encode_jpeg_bound: a capacity no image of that shape can exceed, 0 for arguments pf_encode_jpeg refuses.  Derivation: a block is
+ * at most 22 + 63 * 26 = 1660 bits (longest DC code 11 bits + 11 value bits; 63 coefficients of the longest AC code, 16 bits, + 10
+ * value bits); an interval is its blocks (MCUs of a row x (hs vs + 2)), padded to a byte, every byte stuffed (x 2), + 2 bytes of RSTm
+ * or EOI; the header is 629 bytes.  Generous by a factor of tens for photographs: allocate 3 * height * width and call again with
+ * the bound only where a size comes back negative. */
+int pf_encode_jpeg(pf_handle* h, const uint8_t* images, int mem, int n, int height, int width, int row_stride, int quality,
+                   int subsampling, uint8_t* out, size_t capacity, int* sizes, int out_mem);
+size_t pf_encode_jpeg_bound(int height, int width, int subsampling);
+/* Device memory on the handle's device for callers without a HIP runtime of their own (the Python classes keep the device outputs of
+ * pf_face_redact / pf_face_chips in it, which pf_encode_jpeg then reads).  pf_device_free synchronises the handle's stream first. */
+int pf_device_alloc(pf_handle* h, size_t bytes, void** out);
+int pf_device_free(pf_handle* h, void* p);
+
 /* FaceAna.run(image) / reset() for ONE video stream with the tracking state on the device.  The
  * reference keeps track_box, the previous landmark sets and their displacement on the host and walks the boxes through
  * numpy between the two networks (judge_boxs facer.py:144-189, sort_and_filter :120-142, GroupTrack.calculate + the

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 
@@ -107,6 +107,14 @@ def _declare(lib):
     lib.pf_jpeg_info.argtypes = [vp, sz, ip, ip, ip, ip]
     lib.pf_decode_jpeg.argtypes = [vp, vp, sz, ip, ip, C.POINTER(vp), vp]
     lib.pf_decode_jpeg_batch.argtypes = [vp, i, C.POINTER(vp), C.POINTER(sz), i, ip, ip, C.POINTER(vp)]
+    lib.pf_encode_jpeg.argtypes = [vp, vp, i, i, i, i, i, i, i, vp, sz, vp, i]
+    lib.pf_encode_jpeg.restype = i
+    lib.pf_encode_jpeg_bound.argtypes = [i, i, i]
+    lib.pf_encode_jpeg_bound.restype = sz
+    lib.pf_device_alloc.argtypes = [vp, sz, C.POINTER(vp)]
+    lib.pf_device_alloc.restype = i
+    lib.pf_device_free.argtypes = [vp, vp]
+    lib.pf_device_free.restype = i
     lib.pf_set_frame.argtypes = [vp, vp, i, i, i, i, C.POINTER(C.c_ulonglong), ip]
     lib.pf_forget_frames.argtypes = [vp]
     lib.pf_set_option.argtypes = [vp, i, i]
@@ -300,6 +308,8 @@ class Engine:
             self.lib.pf_host_free(p)
         self._pinned = []
         if getattr(self, "h", None) is not None and self.h:
+            for ptr, _ in self.__dict__.pop("_device_buffers", {}).values():
+                self.lib.pf_device_free(self.h, C.c_void_p(ptr))
             if not getattr(self, "_borrowed", False):      # a lane of a BatchEngine belongs to its pf_batch
                 self.lib.pf_destroy(self.h)
             self.h = None
@@ -431,6 +441,15 @@ class Engine:
                                             _ptr(valid), PF_MEM_HOST), "pf_align_faces")
         return chips, mats, valid.astype(bool)
 
+    def align_faces_device(self, frames, kps: np.ndarray, d_chips: int, counts: Optional[np.ndarray] = None, chip_size: int = 112):
+        """align_faces with the chips [F,top_k,S,S,3] written to device memory, enqueued on the handle's stream (no matrices, no
+        valid flags: chips of invalid slots are left as they were)."""
+        k, f64, F, K = _kps_arg(kps)
+        fptr, mem, F, H, W, _keep = self._frames_arg(frames, F)
+        c = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
+        self._check(self.lib.pf_align_faces(self.h, fptr, mem, F, H, W, _ptr(k), f64, PF_MEM_HOST, _ptr(c), K, int(chip_size), _ptr(int(d_chips)),
+                                            None, None, PF_MEM_DEVICE), "pf_align_faces")
+
     def face_chips(self, rows: int, chip_size: int = 112, out=None):
         """Chips of the faces of the handle's last pf_landmarks / pf_run_frames / pf_track_frame / pf_track_streams call, in that
         call's row order (include/peppa_hip.h pf_face_chips): (chips uint8 [rows,S,S,3], mats float64 [rows,2,3], valid bool [rows])."""
@@ -504,6 +523,18 @@ class Engine:
                                              _ptr(sel), K, *_redact_args(mode, labels, strength, pad, colour), _ptr(out), _ptr(valid),
                                              PF_MEM_HOST), "pf_redact_faces")
         return out, valid.astype(bool)
+
+    def redact_faces_device(self, frames, kps: np.ndarray, d_out: int, counts: Optional[np.ndarray] = None,
+                            select: Optional[np.ndarray] = None, mode="mosaic", labels: int = PF_REDACT_FACE_ALL, strength: int = 16,
+                            pad: int = 0, colour=(0, 0, 0)):
+        """redact_faces with the frames [F,H,W,3] written to device memory, enqueued on the handle's stream."""
+        k, f64, F, K = _kps_arg(kps)
+        fptr, mem, F, H, W, _keep = self._frames_arg(frames, F)
+        c = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
+        sel = None if select is None else np.ascontiguousarray(select, np.int32).reshape(F, K)
+        self._check(self.lib.pf_redact_faces(self.h, fptr, mem, F, H, W, _ptr(k), f64, PF_MEM_HOST, _ptr(c), _ptr(sel), K,
+                                             *_redact_args(mode, labels, strength, pad, colour), _ptr(int(d_out)), None, PF_MEM_DEVICE),
+                    "pf_redact_faces")
 
     def face_redact(self, rows: int, select: Optional[np.ndarray] = None, mode="mosaic", labels: int = PF_REDACT_FACE_ALL,
                     strength: int = 16, pad: int = 0, colour=(0, 0, 0)):
@@ -746,6 +777,67 @@ class Engine:
             finally:
                 self.set_option(PF_OPT_JPEG_ENTROPY, before)
         return counts, boxes, kps, scores
+
+    # ---- baseline JPEG encoder (include/peppa_hip.h pf_encode_jpeg) ---------------------------------------------------------------
+    def encode_jpeg_bound(self, height: int, width: int, subsampling: int = 420) -> int:
+        """A capacity no file of that shape exceeds (0: a shape encode_jpeg refuses)."""
+        return int(self.lib.pf_encode_jpeg_bound(int(height), int(width), int(subsampling)))
+
+    def encode_jpeg(self, images, quality: int = 90, subsampling: int = 420, capacity: Optional[int] = None) -> List[bytes]:
+        """Baseline JFIF files of packed BGR images, written on the device, byte for byte what libjpeg(-turbo) writes for the same
+        quality and sampling with one restart interval per MCU row.  images: uint8 [H,W,3] or [n,H,W,3] (the last axis contiguous;
+        rows may be strided), a ``DeviceFrame``, or ``(device pointer, n, H, W)`` of packed images.  capacity: bytes per file slot, default 3 H W + 4096; where a file does not
+        fit, the call is repeated once with ``encode_jpeg_bound``.  Returns one ``bytes`` per image."""
+        if isinstance(images, DeviceFrame):
+            H, W = images.shape[:2]
+            ptr, mem, n, stride, keep = C.c_void_p(images.ptr), PF_MEM_DEVICE, 1, 3 * W, None
+        elif isinstance(images, tuple):
+            d, n, H, W = (int(v) for v in images)
+            ptr, mem, stride, keep = C.c_void_p(d), PF_MEM_DEVICE, 3 * W, None
+        else:
+            a = np.asarray(images)
+            if a.dtype != np.uint8 or a.ndim not in (3, 4) or a.shape[-1] != 3:
+                raise ValueError("images must be uint8 [H,W,3] or [n,H,W,3]")
+            if a.ndim == 3:
+                a = a[None]
+            n, H, W = a.shape[:3]
+            if n and not (a.strides[3] == 1 and a.strides[2] == 3 and a.strides[1] >= 3 * W and a.strides[0] == H * a.strides[1]):
+                a = np.ascontiguousarray(a)
+            ptr, mem, stride, keep = _ptr(a), PF_MEM_HOST, (a.strides[1] if n else 3 * W), a
+        cap = int(capacity) if capacity is not None else 3 * H * W + 4096
+        for attempt in range(2):
+            out = np.empty((max(n, 1), cap), np.uint8)
+            sizes = np.zeros((max(n, 1),), np.int32)
+            self._check(self.lib.pf_encode_jpeg(self.h, ptr, mem, n, H, W, int(stride), int(quality), int(subsampling), _ptr(out), cap,
+                                                _ptr(sizes), PF_MEM_HOST), "pf_encode_jpeg")
+            if (sizes > 0).all():
+                return [out[i, :sizes[i]].tobytes() for i in range(n)]
+            if attempt == 0:
+                cap = self.encode_jpeg_bound(H, W, subsampling)
+        raise PeppaHipError("pf_encode_jpeg: a file exceeded pf_encode_jpeg_bound (sizes %s)" % (sizes.tolist(),))
+
+    def encode_jpeg_device(self, d_images: int, n: int, H: int, W: int, d_out: int, capacity: int, d_sizes: int, quality: int = 90,
+                           subsampling: int = 420, row_stride: int = 0):
+        """Same on device pointers, enqueued on the handle's stream without a read-back: file i at d_out + i * capacity, its length
+        (or -(bytes needed) where it does not fit) in the int32 d_sizes[i].  row_stride 0: packed rows."""
+        self._check(self.lib.pf_encode_jpeg(self.h, _ptr(int(d_images)), PF_MEM_DEVICE, int(n), int(H), int(W), int(row_stride) or 3 * int(W),
+                                            int(quality), int(subsampling), _ptr(int(d_out)), int(capacity), _ptr(int(d_sizes)), PF_MEM_DEVICE),
+                    "pf_encode_jpeg")
+
+    def device_buffer(self, name: str, nbytes: int) -> int:
+        """A device allocation of at least ``nbytes`` that belongs to the engine, kept under ``name`` and grown on demand
+        (pf_device_alloc): where the classes keep device outputs that encode_jpeg reads.  Freed by close()."""
+        bufs = self.__dict__.setdefault("_device_buffers", {})
+        ptr, have = bufs.get(name, (0, 0))
+        if have < nbytes:
+            if ptr:
+                self._check(self.lib.pf_device_free(self.h, C.c_void_p(ptr)), "pf_device_free")
+                bufs.pop(name)
+            p = C.c_void_p(0)
+            self._check(self.lib.pf_device_alloc(self.h, int(nbytes), C.byref(p)), "pf_device_alloc")
+            ptr = p.value
+            bufs[name] = (ptr, int(nbytes))
+        return ptr
 
     def imread(self, path_or_bytes, want_host: bool = True) -> "DeviceFrame":
         """cv2.imread(path) for baseline JPEG files, decoded into device memory (see decode_jpeg)."""
@@ -1033,6 +1125,21 @@ class BatchEngine:
         sel = None if select is None else np.ascontiguousarray(select, np.int32).reshape(int(rows))
         self._check(self.lib.pf_batch_face_redact(self.b, int(rows), _ptr(sel), *_redact_args(mode, labels, strength, pad, colour),
                                                   _ptr(d_out), _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE), "pf_batch_face_redact")
+
+    def encode_jpeg(self, images, **kw):
+        """``Engine.encode_jpeg`` on lane 0's engine."""
+        return self.lane(0).encode_jpeg(images, **kw)
+
+    def device_buffer(self, name: str, nbytes: int) -> int:
+        return self.lane(0).device_buffer(name, nbytes)
+
+    def encode_jpeg_bound(self, height: int, width: int, subsampling: int = 420) -> int:
+        return self.lane(0).encode_jpeg_bound(height, width, subsampling)
+
+    def encode_jpeg_device(self, d_images: int, n: int, H: int, W: int, d_out: int, capacity: int, d_sizes: int, **kw):
+        """``Engine.encode_jpeg_device`` on lane 0's stream; images the other lanes wrote (face_redact_device, face_chips_device) need
+        a ``sync()`` in front."""
+        return self.lane(0).encode_jpeg_device(d_images, n, H, W, d_out, capacity, d_sizes, **kw)
 
     def close(self):
         self._host.close()

@@ -20,7 +20,7 @@ from ...logger.logger import logger
 from ...graph.detector import build_detector_program
 from ...graph.student import build_student_program
 from ..smoother.lk import EmaFilter
-from .facer import _box_iou, _load_weights, attach_masks, get_cfg, stage_options
+from .facer import _box_iou, _load_weights, attach_masks, get_cfg, jpeg_chips, jpeg_options, jpeg_redacted, stage_options
 from .hip_model_base import _RANGE_ERR
 
 
@@ -28,8 +28,12 @@ class FrameBatchRunner:
     def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, lanes: int = 3, frames_per_lane: int = 32,
                  device: Optional[int] = None, library: Optional[str] = None, graph: bool = True, top_k: Optional[int] = None,
                  face_attributes: Optional[bool] = None, face_chips: Optional[int] = None,
-                 face_masks: Optional[bool] = None, redact: Optional[dict] = None):
-        """``redact`` (default: ``Engine.redact`` of Skps.yml, off): the dict of ``FaceAna``; ``last_redacted`` (uint8 [F,H,W,3])
+                 face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None):
+        """``jpeg`` (default: ``Engine.jpeg`` of the configuration if present, else off): the option of ``FaceAna``;
+        ``last_redacted_jpeg`` (one ``bytes`` per frame of the last ``run``) and ``"chip_jpeg"`` in every result dict, encoded on the
+        GPU (lane 0, behind a synchronisation of the lanes); ``"raw": False`` drops ``last_redacted`` and ``"chip"``.
+
+        ``redact`` (default: ``Engine.redact`` of Skps.yml, off): the dict of ``FaceAna``; ``last_redacted`` (uint8 [F,H,W,3])
         keeps the frames of the last ``run`` with every face the results carry redacted, a frame without a face as a copy.
 
         ``face_masks`` (default: ``Engine.face_masks`` of Skps.yml, false): ``"mask_box"`` and ``"mask"`` in every result dict as in
@@ -46,6 +50,8 @@ class FrameBatchRunner:
         self.face_attributes, self.face_chips, self.face_masks, self.redact = stage_options(eng_cfg, face_attributes, face_chips, face_masks, redact)
         self.last_label_maps = self.last_owner_maps = None
         self.last_redacted = None
+        self.jpeg = jpeg_options(jpeg, eng_cfg)
+        self.last_redacted_jpeg = None
         self.device = int(eng_cfg.get("device", 0)) if device is None else int(device)
         self.dtype = eng_cfg.get("dtype", "f32s")
         root = pathlib.Path(__file__).resolve().parents[2]
@@ -122,8 +128,15 @@ class FrameBatchRunner:
         if self.face_masks:
             lab, own, mb, mv = self.engine.face_masks(F * K)
             masks = (lab, own, mb.reshape(F, K, 4), mv.reshape(F, K))
-        redacted = self.engine.face_redact(F * K, **self.redact)[0] if self.redact else None
-        return r + (attrs, chips, masks, redacted)
+        raw = not self.jpeg or self.jpeg["raw"]
+        redacted = self.engine.face_redact(F * K, **self.redact)[0] if self.redact and raw else None
+        red_jpeg = chip_jpeg = None
+        if self.jpeg and self.redact:
+            red_jpeg = jpeg_redacted(self.engine, self.jpeg, self.redact, F * K, frames.shape, sync=self.engine.sync)
+        if self.jpeg and chips is not None:
+            files = jpeg_chips(self.engine, self.jpeg, F * K, self.face_chips, chips[2], sync=self.engine.sync)
+            chip_jpeg = [files[f * K:(f + 1) * K] for f in range(F)]
+        return r + (attrs, chips, masks, redacted, red_jpeg, chip_jpeg)
 
     def _returned_boxes(self, det_boxes: np.ndarray, kps: np.ndarray) -> np.ndarray:
         """The 'box' a fresh ``FaceAna.run`` hands back (facer.py:81-84): not the detector's box but the hull of the face's
@@ -144,15 +157,16 @@ class FrameBatchRunner:
         the smoothed landmark hull like the reference's, the detector's own box rides along as 'det_box'."""
         frames = np.stack(frames) if isinstance(frames, (list, tuple)) else np.asarray(frames)
         out: List[List[Dict[str, np.ndarray]]] = []
-        all_labels, all_owners, all_redacted = [], [], []
+        all_labels, all_owners, all_redacted, all_red_jpeg = [], [], [], []
+        raw = not self.jpeg or self.jpeg["raw"]
         for s in range(0, frames.shape[0], self.max_frames):
             chunk = frames[s:s + self.max_frames]
-            attrs = chips = masks = redacted = None
+            attrs = chips = masks = redacted = red_jpeg = chip_jpeg = None
             planted = self._planted_rows(chunk) if self._planted_rows is not None else None
             if self.face_attributes or self.face_chips or self.face_masks or self.redact:
                 if chunk.ndim != 4 or chunk.shape[-1] != 3 or chunk.dtype != np.uint8:
                     raise ValueError("frames must be uint8 [F,H,W,3]")
-                counts, boxes, kps, scores, attrs, chips, masks, redacted = self._guarded(self._run_with_extras, chunk, planted)
+                counts, boxes, kps, scores, attrs, chips, masks, redacted, red_jpeg, chip_jpeg = self._guarded(self._run_with_extras, chunk, planted)
             else:
                 counts, boxes, kps, scores = self.run_arrays(chunk, planted)
             for f in range(counts.shape[0]):
@@ -166,8 +180,11 @@ class FrameBatchRunner:
                 if chips is not None:           # cut with the landmarks the result carries; a degenerate fit gets neither key
                     for i, d in enumerate(res):
                         if chips[2][f, i]:
-                            d["chip"] = chips[0][f, i].copy()
+                            if raw:
+                                d["chip"] = chips[0][f, i].copy()
                             d["chip_matrix"] = chips[1][f, i].copy()
+                        if chip_jpeg is not None:
+                            d["chip_jpeg"] = chip_jpeg[f][i]
                 if masks is not None:
                     attach_masks(res, masks[0][f], masks[1][f], masks[2][f], masks[3][f])
                 out.append(res)
@@ -175,10 +192,14 @@ class FrameBatchRunner:
                 all_labels.append(masks[0]); all_owners.append(masks[1])
             if redacted is not None:
                 all_redacted.append(redacted)
+            if red_jpeg is not None:
+                all_red_jpeg += red_jpeg
         if self.face_masks and all_labels:
             self.last_label_maps, self.last_owner_maps = np.concatenate(all_labels), np.concatenate(all_owners)
         if all_redacted:
             self.last_redacted = np.concatenate(all_redacted)
+        if all_red_jpeg:
+            self.last_redacted_jpeg = all_red_jpeg
         return out
 
     def close(self):

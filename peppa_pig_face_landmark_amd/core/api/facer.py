@@ -101,6 +101,58 @@ def redact_options(value, eng_cfg):
     return opts
 
 
+def jpeg_options(value, eng_cfg):
+    """The ``jpeg`` option of the classes: ``None`` -> ``Engine.jpeg`` of the configuration if present, else off (``None`` is
+    returned); a quality (int) or a dict with any of "quality" (90), "subsampling" (420) and "raw" (True: the raw host copies are kept
+    next to the files)."""
+    if value is None:
+        value = eng_cfg.get("jpeg", None)
+    if value is None or value is False:
+        return None
+    opts = {"quality": 90, "subsampling": 420, "raw": True}
+    if isinstance(value, dict):
+        unknown = set(value) - set(opts)
+        if unknown:
+            raise ValueError("jpeg: unknown keys %s" % sorted(unknown))
+        opts.update(value)
+    elif value is not True:
+        opts["quality"] = int(value)
+    return opts
+
+
+def jpeg_redacted(engine, jpeg, redact, rows, shape, source=None, sync=None):
+    """The redacted frames [F,H,W,3] (``shape``) as JPEG files, redacted and encoded on the device: pf_face_redact of the last call's
+    first ``rows`` rows, or -- ``source = (frames argument, landmarks)`` -- pf_redact_faces, into device memory the engine keeps,
+    then pf_encode_jpeg on it; only the files come to the host.  ``sync``: called between the two where they run on different
+    streams (BatchEngine)."""
+    F, H, W = (int(v) for v in shape[:3])
+    d = engine.device_buffer("jpeg_redacted", F * H * W * 3)
+    if source is None:
+        engine.face_redact_device(rows, d, **redact)
+    else:
+        engine.redact_faces_device(source[0], source[1], d, **redact)
+    if sync is not None:
+        sync()
+    return engine.encode_jpeg((d, F, H, W), quality=jpeg["quality"], subsampling=jpeg["subsampling"])
+
+
+def jpeg_chips(engine, jpeg, rows, S, valid, source=None, sync=None):
+    """One JPEG file per valid chip of ``rows`` chips (``None`` for an invalid one), cut and encoded on the device (pf_face_chips, or
+    pf_align_faces for ``source = (frames argument, landmarks)``, then pf_encode_jpeg)."""
+    rows, S = int(rows), int(S)
+    if rows == 0:
+        return []
+    d = engine.device_buffer("jpeg_chips", rows * S * S * 3)
+    if source is None:
+        engine.face_chips_device(rows, S, d)
+    else:
+        engine.align_faces_device(source[0], source[1], d, chip_size=S)
+    if sync is not None:
+        sync()
+    files = engine.encode_jpeg((d, rows, S, S), quality=jpeg["quality"], subsampling=jpeg["subsampling"])
+    return [f if v else None for f, v in zip(files, np.asarray(valid).reshape(-1))]
+
+
 def stage_options(eng_cfg, face_attributes=None, face_chips=None, face_masks=None, redact=None):
     """The four options FaceAna, StreamTracker and FrameBatchRunner share, each from its argument or, when that is ``None``, from
     ``Engine`` of Skps.yml: (face_attributes bool, face_chips int (0 = off), face_masks bool, redact dict or None)."""
@@ -118,8 +170,16 @@ def host_frame(image) -> np.ndarray:
 class FaceAna:
     def __init__(self, verbose: bool = False, cfg: Optional[dict] = None, weights: Optional[dict] = None,
                  device: Optional[int] = None, library: Optional[str] = None, face_attributes: Optional[bool] = None,
-                 face_chips: Optional[int] = None, face_masks: Optional[bool] = None, redact: Optional[dict] = None):
-        """``redact`` (default: ``Engine.redact`` of Skps.yml, off): a dict with any of ``"mode"`` ("fill" / "mosaic" / "blur"),
+                 face_chips: Optional[int] = None, face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None):
+        """``jpeg`` (default: ``Engine.jpeg`` of the configuration if present, else off): a quality, or a dict with any of
+        ``"quality"`` (90), ``"subsampling"`` (420, 422 or 444) and ``"raw"`` (True).  With ``redact`` on it keeps
+        ``last_redacted_jpeg`` (bytes: the frame ``last_redacted`` holds as a baseline JPEG file); with ``face_chips`` on every result
+        gets ``"chip_jpeg"`` (bytes, ``None`` for a degenerate fit).  Both are encoded on the GPU from the device outputs of the
+        redaction and of the chips (``Engine.encode_jpeg``), byte for byte what libjpeg writes with one restart interval per MCU row.
+        ``"raw": False`` drops the raw host copies: ``last_redacted`` stays ``None`` -- the redacted frame then crosses PCIe only as
+        its file -- and the results carry no ``"chip"``.
+
+        ``redact`` (default: ``Engine.redact`` of Skps.yml, off): a dict with any of ``"mode"`` ("fill" / "mosaic" / "blur"),
         ``"labels"`` (bit L = face-region label L, bit 0 the background, 0x200 the face boxes grown by ``"pad"``), ``"strength"``
         (mosaic cell 4 / 8 / 16, blur radius 1..32), ``"pad"`` and ``"colour"`` keeps ``last_redacted`` (uint8 [H,W,3]): the frame
         with every face the result carries redacted on the GPU from its landmarks, every other pixel untouched; a frame without a
@@ -161,6 +221,8 @@ class FaceAna:
         self.face_attributes, self.face_chips, self.face_masks, self.redact = stage_options(eng_cfg, face_attributes, face_chips, face_masks, redact)
         self.last_label_map = self.last_owner_map = None
         self.last_redacted = None
+        self.jpeg = jpeg_options(jpeg, eng_cfg)
+        self.last_redacted_jpeg = None
         self._planted_rows = None    # test instrument: callable returning decoded detector rows that replace the detector's own
         self._det_cfg = sk["Detect"]
         self.top_k = sk["Detect"]["topk"]
@@ -189,10 +251,13 @@ class FaceAna:
         if self.device_tracking:
             def fn(*args):       # the attribute rows / chips of the tracked faces, compacted like kps (pf_face_attrs / pf_face_chips after pf_track_frame)
                 r = self.engine.track_frame(*args)
-                return r + (self.engine.face_attrs(len(r[0])) if self.face_attributes else None,
-                            self.engine.face_chips(len(r[0]), self.face_chips) if self.face_chips and len(r[0]) else None,
-                            self.engine.face_masks(len(r[0])) if self.face_masks and len(r[0]) else None,
-                            self.engine.face_redact(len(r[0]), **self.redact)[0] if self.redact and len(r[0]) else None)
+                n = len(r[0])
+                chips = self.engine.face_chips(n, self.face_chips) if self.face_chips and n else None
+                jp = (jpeg_redacted(self.engine, self.jpeg, self.redact, n, (1,) + tuple(image.shape[:2])) if self.jpeg and self.redact and n else None,
+                      jpeg_chips(self.engine, self.jpeg, n, self.face_chips, chips[2]) if self.jpeg and chips is not None else None)
+                return r + (self.engine.face_attrs(n) if self.face_attributes else None, chips,
+                            self.engine.face_masks(n) if self.face_masks and n else None,
+                            self.engine.face_redact(n, **self.redact)[0] if self.redact and n and self._raw else None, jp)
             out = run_guarded(
                 [self.face_detector.model, self.face_landmark.model], fn, image, float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]),
                 float(self.min_face), int(self.top_k), float(self.iou_thres), float(self.alpha), float(self.diff_thres),
@@ -200,8 +265,8 @@ class FaceAna:
             boxes, kps, scores = out[:3]
             self.previous_image = image
             self.track_box = boxes
-            self._keep_redacted(out[7], image)
-            return self.to_dict(boxes, kps, scores, out[4], out[5], self._keep_masks(out[6], image))
+            self._keep_redacted(out[7], image, out[8][0])
+            return self.to_dict(boxes, kps, scores, out[4], out[5], self._keep_masks(out[6], image), out[8][1], self._raw)
         diff = self.engine.set_frame(image)
         self.previous_image = image
         if diff is None or self.track_box is None or diff > self.diff_thres:
@@ -224,19 +289,36 @@ class FaceAna:
         if self.face_chips and len(landmarks):      # cut with the smoothed landmarks the result carries, from the resident frame
             c, m, v = self.engine.align_faces(None, np.asarray(landmarks)[None], chip_size=self.face_chips)
             chips = (c[0], m[0], v[0])
+        chip_jpeg = None
+        if self.jpeg and chips is not None:
+            chip_jpeg = jpeg_chips(self.engine, self.jpeg, len(landmarks), self.face_chips, chips[2], source=(None, np.asarray(landmarks)[None]))
         masks = None
         if self.face_masks and len(landmarks):      # filled from the smoothed landmarks the result carries
             masks = self.engine.mask_faces(np.asarray(landmarks)[None], image.shape[0], image.shape[1])
-        redacted = None
+        redacted = red_jpeg = None
         if self.redact and len(landmarks):          # from the resident frame, with the smoothed landmarks the result carries
-            redacted = self.engine.redact_faces(None, np.asarray(landmarks)[None], **self.redact)[0]
-        self._keep_redacted(redacted, image)
-        return self.to_dict(self.track_box, landmarks, states, attrs, chips, self._keep_masks(masks, image))
+            if self._raw:
+                redacted = self.engine.redact_faces(None, np.asarray(landmarks)[None], **self.redact)[0]
+            if self.jpeg:
+                red_jpeg = jpeg_redacted(self.engine, self.jpeg, self.redact, len(landmarks), (1,) + tuple(image.shape[:2]),
+                                         source=(None, np.asarray(landmarks)[None]))
+        self._keep_redacted(redacted, image, red_jpeg)
+        return self.to_dict(self.track_box, landmarks, states, attrs, chips, self._keep_masks(masks, image), chip_jpeg, self._raw)
 
-    def _keep_redacted(self, redacted, image):
-        """[1,H,W,3] of Engine.redact_faces / face_redact, or None when the frame has no face -> last_redacted."""
-        if self.redact:
+    @property
+    def _raw(self) -> bool:
+        """Are the raw host copies kept (always without the ``jpeg`` option)?"""
+        return not self.jpeg or bool(self.jpeg["raw"])
+
+    def _keep_redacted(self, redacted, image, red_jpeg=None):
+        """[1,H,W,3] of Engine.redact_faces / face_redact, or None when the frame has no face -> last_redacted; the files of
+        jpeg_redacted (None: no face, the frame itself is encoded) -> last_redacted_jpeg."""
+        if self.redact and self._raw:
             self.last_redacted = host_frame(image) if redacted is None else redacted[0]
+        if self.redact and self.jpeg:
+            self.last_redacted_jpeg = red_jpeg[0] if red_jpeg is not None else self.engine.encode_jpeg(
+                image if isinstance(image, _native.DeviceFrame) else np.asarray(image), quality=self.jpeg["quality"],
+                subsampling=self.jpeg["subsampling"])[0]
 
     def _keep_masks(self, masks, image):
         """(labels [1,H,W], owners, boxes, valid) of Engine.mask_faces / face_masks -> the one frame's (labels, owners, boxes [n,4],
@@ -275,8 +357,8 @@ class FaceAna:
             return frame
 
     @staticmethod
-    def to_dict(bboxes, kps, states, attrs=None, chips=None, masks=None):
-        """``chips``: (chips [n,S,S,3], matrices [n,2,3], valid [n]) of the same rows (Engine.face_chips / align_faces).
+    def to_dict(bboxes, kps, states, attrs=None, chips=None, masks=None, chip_jpeg=None, raw_chips=True):
+        """``chip_jpeg``: one file (or None) per row, of jpeg_chips; ``raw_chips`` False: no ``"chip"`` key.  ``chips``: (chips [n,S,S,3], matrices [n,2,3], valid [n]) of the same rows (Engine.face_chips / align_faces).
         ``masks``: (labels [H,W], owners [H,W], boxes [>= n,4], valid [>= n]) of the rows' frame, row i being slot i
         (Engine.face_masks / mask_faces)."""
         out = [{"box": bboxes[i], "kps": kps[i], "scores": states[i]} for i in range(len(bboxes))]
@@ -287,8 +369,12 @@ class FaceAna:
         if chips is not None:
             for i, d in enumerate(out):
                 if chips[2][i]:
-                    d["chip"] = chips[0][i].copy()
+                    if raw_chips:
+                        d["chip"] = chips[0][i].copy()
                     d["chip_matrix"] = chips[1][i].copy()
+        if chip_jpeg is not None:
+            for i, d in enumerate(out):
+                d["chip_jpeg"] = chip_jpeg[i]
         if masks is not None:
             attach_masks(out, *masks)
         return out

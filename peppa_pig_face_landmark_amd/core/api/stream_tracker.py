@@ -16,7 +16,7 @@ import numpy as np
 
 from ... import _native
 from ...logger.logger import logger
-from .facer import FaceAna, _load_weights, get_cfg, stage_options
+from .facer import FaceAna, _load_weights, get_cfg, jpeg_chips, jpeg_options, jpeg_redacted, stage_options
 from .hip_model_base import HIPEngine, run_guarded
 
 
@@ -24,8 +24,12 @@ class StreamTracker:
     def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, max_streams: int = 8,
                  device: Optional[int] = None, library: Optional[str] = None, verbose: bool = False,
                  face_attributes: Optional[bool] = None, face_chips: Optional[int] = None,
-                 face_masks: Optional[bool] = None, redact: Optional[dict] = None):
-        """``redact`` (default: ``Engine.redact`` of Skps.yml, off): the dict of ``FaceAna``; ``last_redacted`` (stream id -> uint8
+                 face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None):
+        """``jpeg`` (default: ``Engine.jpeg`` of the configuration if present, else off): the option of ``FaceAna``;
+        ``last_redacted_jpeg`` (stream id -> bytes) and ``"chip_jpeg"`` in every result dict, encoded on the GPU; ``"raw": False``
+        drops ``last_redacted`` and ``"chip"``.
+
+        ``redact`` (default: ``Engine.redact`` of Skps.yml, off): the dict of ``FaceAna``; ``last_redacted`` (stream id -> uint8
         [H,W,3]) keeps the frames of the last call with every face the results carry redacted.
 
         ``face_masks`` (default: ``Engine.face_masks`` of Skps.yml, false): ``"mask_box"`` and ``"mask"`` in every result dict as in
@@ -54,6 +58,8 @@ class StreamTracker:
 
         self.face_attributes, self.face_chips, self.face_masks, self.redact = stage_options(eng_cfg, face_attributes, face_chips, face_masks, redact)
         self.last_redacted: Optional[Dict[int, np.ndarray]] = None
+        self.jpeg = jpeg_options(jpeg, eng_cfg)
+        self.last_redacted_jpeg: Optional[Dict[int, bytes]] = None
         self.last_label_maps: Dict[int, np.ndarray] = {}
         self.last_owner_maps: Dict[int, np.ndarray] = {}
         self.max_streams = int(max_streams)
@@ -86,30 +92,39 @@ class StreamTracker:
 
         def call(*args):
             r = self.engine.track_streams(*args)
-            attrs = chips = masks = redacted = None
-            if self.redact:
+            attrs = chips = masks = redacted = red_jpeg = chip_jpeg = None
+            raw = not self.jpeg or self.jpeg["raw"]
+            if self.redact and raw:
                 redacted = self.engine.face_redact(len(r) * K, **self.redact)[0]      # one frame per listed stream
+            if self.redact and self.jpeg:
+                red_jpeg = jpeg_redacted(self.engine, self.jpeg, self.redact, len(r) * K, batch.shape)
             if self.face_attributes:
                 a = self.engine.face_attrs(len(r) * K)           # [n][top_k] rows, compacted like kps
                 attrs = [a[i * K:i * K + len(b)] for i, (b, _, _, _) in enumerate(r)]
             if self.face_chips:
                 c = self.engine.face_chips(len(r) * K, self.face_chips)      # the same rows
                 chips = [tuple(x[i * K:i * K + len(b)] for x in c) for i, (b, _, _, _) in enumerate(r)]
+                if self.jpeg:
+                    files = jpeg_chips(self.engine, self.jpeg, len(r) * K, self.face_chips, c[2])
+                    chip_jpeg = [files[i * K:i * K + len(b)] for i, (b, _, _, _) in enumerate(r)]
             if self.face_masks:
                 lab, own, mb, mv = self.engine.face_masks(len(r) * K)        # one map per listed stream, slots = the same rows
                 masks = [(lab[i], own[i], mb[i * K:(i + 1) * K], mv[i * K:(i + 1) * K]) for i in range(len(r))]
-            return r, attrs, chips, masks, redacted
-        res, attrs, chips, masks, redacted = run_guarded([self.detector, self.landmark], call, ids, batch,
+            return r, attrs, chips, masks, redacted, red_jpeg, chip_jpeg
+        res, attrs, chips, masks, redacted, red_jpeg, chip_jpeg = run_guarded([self.detector, self.landmark], call, ids, batch,
                                  float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]), float(self.min_face),
                                  float(self.iou_thres), float(self.alpha), float(self.diff_thres), planted)
         self.last_detector_ran = {s: ran for s, (_, _, _, ran) in zip(ids, res)}   # did the gate run the detector
         if redacted is not None:
             self.last_redacted = {s: redacted[i] for i, s in enumerate(ids)}
+        if red_jpeg is not None:
+            self.last_redacted_jpeg = {s: red_jpeg[i] for i, s in enumerate(ids)}
         if masks is not None:
             self.last_label_maps = {s: m[0] for s, m in zip(ids, masks)}
             self.last_owner_maps = {s: m[1] for s, m in zip(ids, masks)}
         return {s: self.to_dict(b, k, sc, attrs[i] if attrs is not None else None, chips[i] if chips is not None else None,
-                                masks[i] if masks is not None else None)
+                                masks[i] if masks is not None else None, chip_jpeg[i] if chip_jpeg is not None else None,
+                                not self.jpeg or self.jpeg["raw"])
                 for i, (s, (b, k, sc, _)) in enumerate(zip(ids, res))}
 
     to_dict = staticmethod(FaceAna.to_dict)

@@ -32,6 +32,7 @@
 #include "k_pwhead.h"
 #include "k_mbx_args.h"
 #include "k_jpeg.h"
+#include "k_jpeg_enc.h"
 #include "k_prepost.h"
 #include "k_track.h"
 #include "k_align.h"
@@ -108,6 +109,7 @@ struct pf_handle {
     TrackPool track;
     TrackPool streams;
     JpegState jpeg;          // pf_decode_jpeg (jpeg.inl)
+    JpegEncState jpeg_enc;   // pf_encode_jpeg (jpeg_enc.inl): tables and scratch of its three kernels
     // f32s range guard (pf_common.h pf_amax, k_layers.h range_verdict_kernel): on for every forward unless switched off with
     // PF_OPT_RANGE_CHECK = 0; the slots live with each program
     int range_every = 1;
@@ -508,6 +510,7 @@ void pf_destroy(pf_handle* h) {
     h->track.release();
     h->streams.release();
     h->jpeg.release();
+    h->jpeg_enc.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -757,4 +760,5 @@ int pf_profile_fetch(pf_handle* h, char* names, size_t names_cap, float* ms, int
 #include "comm.inl"
 #include "track.inl"
 #include "jpeg.inl"
+#include "jpeg_enc.inl"
 #include "batch.inl"

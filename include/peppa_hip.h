@@ -184,6 +184,43 @@ int pf_redact_faces(pf_handle* h, const uint8_t* frames, int mem, int n_frames, 
 int pf_face_redact(pf_handle* h, int rows, const int* select, int mode, int label_mask, int strength, int pad, unsigned colour,
                    uint8_t* out, int* valid, int out_mem);
 
+/* Face overlay (kernels draw_prims_kernel / draw_kernel, csrc/k_draw.h): out [F][H][W][3] packed BGR, EVERY byte
+ * written -- a disc on each of the 98 landmarks, the 103 contour edges of the label maps' regions as round-capped lines and the
+ * outline of the clipped box, blended once onto a copy of the frame; every uncovered pixel is its input byte for byte.  The rule is
+ * exact and integer on the Q4 vertices of pf_mask_faces (all 98 landmarks; a pupil that is not finite is not drawn), with
+ * P = (16 px, 16 py) the centre of pixel (px, py):
+ *   disc (C, R)       covers P iff |P - C|^2 <= R^2
+ *   PF_DRAW_POINTS    landmark i: the disc of R = 16 point_radius; colour_hi iff scores == NULL or scores[i] > score_thres in float32
+ *                     (NaN and equality are lo), else colour_lo
+ *   PF_DRAW_CONTOURS  edge A -> B of the region table, d = B - A, q = P - A, w = line_width: covered iff d.d > 0 and 0 <= q.d <= d.d and
+ *                     (q x d)^2 <= 64 w^2 d.d, or a disc of R = 8 w about A or B covers P
+ *   PF_DRAW_BOX       the clipped box (x0, y0, x1, y1) of pf_mask_faces, if x1 > x0 and y1 > y0: x0 - w <= px < x1 + w and
+ *                     y0 - w <= py < y1 + w and not inside the box
+ * Among the primitives that cover a pixel the lowest valid slot wins, within it points beat contours beat the box, among points the
+ * highest index.  Exactly one colour c is applied, once: (in (256 - alpha) + c alpha + 128) >> 8 per channel (low byte of a colour =
+ * channel 0).  frames, mem, kps, kps_f64, kps_mem, counts, top_k, valid and out_mem as for pf_redact_faces; scores (optional)
+ * [F][top_k][98] float32 in the memory of kps.  out must not alias the frames.  LIMITS: out of place only, hard edges, no text. */
+#define PF_DRAW_POINTS   1
+#define PF_DRAW_CONTOURS 2
+#define PF_DRAW_BOX      4
+typedef struct pf_draw_style {
+    int what;              /* bits above, at least one */
+    int point_radius;      /* r, 1..16 pixels */
+    int line_width;        /* w, 1..16 pixels: contours and box */
+    int alpha;             /* a, 1..256; 256 = opaque */
+    float score_thres;     /* a point is "hi" iff scores given and score > score_thres; scores NULL: all hi */
+    unsigned colour_hi, colour_lo, colour_contour, colour_box;   /* low byte = channel 0, as pf_redact_faces */
+} pf_draw_style;
+int pf_draw_faces(pf_handle* h, const uint8_t* frames, int mem, int n_frames, int height, int width,
+                  const void* kps, int kps_f64, int kps_mem, const int* counts, const float* scores, int top_k,
+                  const pf_draw_style* style, uint8_t* out, int* valid, int out_mem);
+/* The frames of the handle's last pipeline call with its faces drawn: rows, refusals and messages those of pf_face_redact.  scores
+ * (optional) is [rows][98] in HOST memory.  base (optional) is a DEVICE pointer to [ceil(rows / per_frame)][H][W][3] packed frames
+ * drawn on in place of the frames of the last call (pf_face_redact to the device, then this); it must not alias out.  rows == 0
+ * succeeds and writes nothing.  The record of the last call is left alone. */
+int pf_face_draw(pf_handle* h, int rows, const float* scores, const pf_draw_style* style,
+                 const uint8_t* base, uint8_t* out, int* valid, int out_mem);
+
 /* Detector forward == session.run of yolov5n-0.5.onnx (face_detector.py:29-31):
  * input float32 NCHW [1][3][384][640] RGB/255 or uint8 NHWC letterboxed RGB;
  * output [rows][16] decoded rows (cx,cy,w,h,obj,10 landmark coords,cls), rows = 15120 at 384x640. */
@@ -460,6 +497,10 @@ int pf_batch_face_masks_shape(pf_batch* b, int rows, int* n_frames, int* height,
  * laid out like its kps.  Device-resident frames of that call must still be alive. */
 int pf_batch_face_redact(pf_batch* b, int rows, const int* select, int mode, int label_mask, int strength, int pad, unsigned colour,
                          uint8_t* out, int* valid, int out_mem);
+/* pf_face_draw of the lanes, gathered the same way: each lane draws the frames it ran, front mode on or off; scores [rows][98] in host
+ * memory; base (optional, device) and out are [n_frames][H][W][3] and offset per lane. */
+int pf_batch_face_draw(pf_batch* b, int rows, const float* scores, const pf_draw_style* style,
+                       const uint8_t* base, uint8_t* out, int* valid, int out_mem);
 
 /* Engine options.  PF_OPT_HIP_GRAPH = 1: pf_run_frames* calls whose buffers all live on the device are captured
  * into a hipGraph per distinct (pointers, shapes, thresholds) and replayed (launch-latency bound small batches). */

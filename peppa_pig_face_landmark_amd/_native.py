@@ -78,6 +78,12 @@ def _declare(lib):
         lib.pf_batch_face_redact.argtypes = [vp, i, vp, i, i, i, i, u, vp, vp, i]
         for name in ("pf_redact_faces", "pf_face_redact", "pf_batch_face_redact"):
             getattr(lib, name).restype = i
+    if hasattr(lib, "pf_draw_faces"):      # likewise
+        lib.pf_draw_faces.argtypes = [vp, vp, i, i, i, i, vp, i, i, vp, vp, i, vp, vp, vp, i]
+        lib.pf_face_draw.argtypes = [vp, i, vp, vp, vp, vp, vp, i]
+        lib.pf_batch_face_draw.argtypes = [vp, i, vp, vp, vp, vp, vp, i]
+        for name in ("pf_draw_faces", "pf_face_draw", "pf_batch_face_draw"):
+            getattr(lib, name).restype = i
     lib.pf_detect.argtypes = [vp, vp, i, i, i, i, f, f, fp, i, ip]
     lib.pf_landmarks.argtypes = [vp, vp, i, i, i, i, fp, i, fp, fp, ip]
     lib.pf_landmarks_f64.argtypes = [vp, vp, i, i, i, i, C.POINTER(C.c_double), i, fp, fp, ip]
@@ -246,6 +252,52 @@ def _last_call_redact(check, fn, fn_shape, handle, what, rows, select, args):
     valid = np.zeros((rows,), np.int32)
     sel = None if select is None else np.ascontiguousarray(select, np.int32).reshape(rows)
     check(fn(handle, rows, _ptr(sel), *args, _ptr(out), _ptr(valid), PF_MEM_HOST), what)
+    return out, valid.astype(bool)
+
+
+PF_DRAW_POINTS, PF_DRAW_CONTOURS, PF_DRAW_BOX = 1, 2, 4
+_DRAW_WHAT = {"points": PF_DRAW_POINTS, "contours": PF_DRAW_CONTOURS, "box": PF_DRAW_BOX}
+
+
+class DrawStyle(C.Structure):
+    """pf_draw_style of include/peppa_hip.h."""
+    _fields_ = [("what", C.c_int), ("point_radius", C.c_int), ("line_width", C.c_int), ("alpha", C.c_int), ("score_thres", C.c_float),
+                ("colour_hi", C.c_uint), ("colour_lo", C.c_uint), ("colour_contour", C.c_uint), ("colour_box", C.c_uint)]
+
+
+def _colour_arg(colour):
+    if not isinstance(colour, (int, np.integer)):
+        c = [int(v) & 255 for v in colour]
+        colour = c[0] | (c[1] << 8) | (c[2] << 16)
+    return int(colour) & 0xFFFFFFFF
+
+
+def _draw_style(what=("points",), point_radius=2, line_width=1, alpha=256, score_thres=0.8, colour_hi=(255, 255, 255),
+                colour_lo=(0, 0, 255), colour_contour=(0, 255, 0), colour_box=(255, 255, 0)):
+    """The overlay's parameters as the C ABI takes them; what is the bit mask or names out of "points", "contours", "box";
+    a colour is an int (the low byte is channel 0) or a (c0, c1, c2) tuple."""
+    if isinstance(what, str):
+        what = (what,)
+    if not isinstance(what, (int, np.integer)):
+        bits = 0
+        for w in what:
+            if w not in _DRAW_WHAT:
+                raise ValueError("what holds 'points', 'contours' and 'box' (got %r)" % (w,))
+            bits |= _DRAW_WHAT[w]
+        what = bits
+    return DrawStyle(int(what), int(point_radius), int(line_width), int(alpha), float(score_thres), _colour_arg(colour_hi),
+                     _colour_arg(colour_lo), _colour_arg(colour_contour), _colour_arg(colour_box))
+
+
+def _last_call_draw(check, fn, fn_shape, handle, what, rows, scores, base, style):
+    """Host-output pf_face_draw / pf_batch_face_draw: the frames take the shape the library reports for `rows`."""
+    rows = int(rows)
+    F, H, W = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(fn_shape(handle, rows, C.byref(F), C.byref(H), C.byref(W)), what)
+    out = np.zeros((F.value, H.value, W.value, 3), np.uint8)
+    valid = np.zeros((rows,), np.int32)
+    sc = None if scores is None else np.ascontiguousarray(scores, np.float32).reshape(rows, 98)
+    check(fn(handle, rows, _ptr(sc), C.byref(style), _ptr(int(base)) if base else None, _ptr(out), _ptr(valid), PF_MEM_HOST), what)
     return out, valid.astype(bool)
 
 
@@ -550,6 +602,50 @@ class Engine:
         sel = None if select is None else np.ascontiguousarray(select, np.int32).reshape(int(rows))
         self._check(self.lib.pf_face_redact(self.h, int(rows), _ptr(sel), *_redact_args(mode, labels, strength, pad, colour), _ptr(d_out),
                                             _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE), "pf_face_redact")
+
+    # ---- face overlay (include/peppa_hip.h pf_draw_faces / pf_face_draw) ------------------------------------------------------------
+    def draw_faces(self, frames, kps: np.ndarray, counts: Optional[np.ndarray] = None, scores: Optional[np.ndarray] = None, out=None,
+                   **style):
+        """Frames with the landmarks, contours and boxes of their faces drawn on, every other pixel untouched.  frames, kps and counts
+        as for redact_faces; scores: float32 [F,top_k,98] (None: every point takes colour_hi); style: what=("points",) out of
+        "points" / "contours" / "box", point_radius=2, line_width=1, alpha=256, score_thres=0.8, colour_hi, colour_lo, colour_contour,
+        colour_box.  Returns (out uint8 [F,H,W,3], valid bool [F,top_k])."""
+        st = _draw_style(**style)
+        k, f64, F, K = _kps_arg(kps)
+        fptr, mem, F, H, W, _keep = self._frames_arg(frames, F)
+        c = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
+        sc = None if scores is None else np.ascontiguousarray(scores, np.float32).reshape(F, K, 98)
+        if out is None:
+            out = np.zeros((F, H, W, 3), np.uint8)
+        valid = np.zeros((F, K), np.int32)
+        self._check(self.lib.pf_draw_faces(self.h, fptr, mem, F, H, W, _ptr(k), f64, PF_MEM_HOST, _ptr(c), _ptr(sc), K, C.byref(st),
+                                           _ptr(out), _ptr(valid), PF_MEM_HOST), "pf_draw_faces")
+        return out, valid.astype(bool)
+
+    def draw_faces_device(self, frames, kps: np.ndarray, d_out: int, counts: Optional[np.ndarray] = None,
+                          scores: Optional[np.ndarray] = None, **style):
+        """draw_faces with the frames [F,H,W,3] written to device memory, enqueued on the handle's stream."""
+        st = _draw_style(**style)
+        k, f64, F, K = _kps_arg(kps)
+        fptr, mem, F, H, W, _keep = self._frames_arg(frames, F)
+        c = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
+        sc = None if scores is None else np.ascontiguousarray(scores, np.float32).reshape(F, K, 98)
+        self._check(self.lib.pf_draw_faces(self.h, fptr, mem, F, H, W, _ptr(k), f64, PF_MEM_HOST, _ptr(c), _ptr(sc), K, C.byref(st),
+                                           _ptr(int(d_out)), None, PF_MEM_DEVICE), "pf_draw_faces")
+
+    def face_draw(self, rows: int, scores: Optional[np.ndarray] = None, base: int = 0, **style):
+        """The frames of the handle's last pf_landmarks / pf_run_frames / pf_track_frame / pf_track_streams call with the faces of its
+        first ``rows`` rows drawn on (include/peppa_hip.h pf_face_draw): (out uint8 [F,H,W,3], valid bool [rows]).  scores: [rows,98];
+        base: a device pointer to [F,H,W,3] frames to draw on instead (face_redact_device wrote them), 0 for the call's own."""
+        return _last_call_draw(self._check, self.lib.pf_face_draw, self.lib.pf_face_masks_shape, self.h, "pf_face_draw", rows, scores,
+                               base, _draw_style(**style))
+
+    def face_draw_device(self, rows: int, d_out: int, scores: Optional[np.ndarray] = None, d_base: int = 0, d_valid: int = 0, **style):
+        """Same into device memory (sized by face_masks_shape), enqueued on the handle's stream."""
+        st = _draw_style(**style)
+        sc = None if scores is None else np.ascontiguousarray(scores, np.float32).reshape(int(rows), 98)
+        self._check(self.lib.pf_face_draw(self.h, int(rows), _ptr(sc), C.byref(st), _ptr(int(d_base)) if d_base else None, _ptr(int(d_out)),
+                                          _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE), "pf_face_draw")
 
     def landmark_forward_device(self, d_input: int, kind: int, batch: int, d_loc: int = 0, d_score: int = 0):
         """Same on device pointers (bench): nothing crosses PCIe."""
@@ -1125,6 +1221,23 @@ class BatchEngine:
         sel = None if select is None else np.ascontiguousarray(select, np.int32).reshape(int(rows))
         self._check(self.lib.pf_batch_face_redact(self.b, int(rows), _ptr(sel), *_redact_args(mode, labels, strength, pad, colour),
                                                   _ptr(d_out), _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE), "pf_batch_face_redact")
+
+    def draw_faces(self, frames, kps, **kw):
+        """Stage-level overlay on lane 0's engine (``Engine.draw_faces``)."""
+        return self.lane(0).draw_faces(frames, kps, **kw)
+
+    def face_draw(self, rows: int, scores: Optional[np.ndarray] = None, base: int = 0, **style):
+        """The frames of the last run_frames* call with their faces drawn on (include/peppa_hip.h pf_batch_face_draw), as
+        ``Engine.face_draw`` returns them; each lane draws the frames it ran."""
+        return _last_call_draw(self._check, self.lib.pf_batch_face_draw, self.lib.pf_batch_face_masks_shape, self.b,
+                               "pf_batch_face_draw", rows, scores, base, _draw_style(**style))
+
+    def face_draw_device(self, rows: int, d_out: int, scores: Optional[np.ndarray] = None, d_base: int = 0, d_valid: int = 0, **style):
+        """Same into device memory, enqueued on the lanes' streams."""
+        st = _draw_style(**style)
+        sc = None if scores is None else np.ascontiguousarray(scores, np.float32).reshape(int(rows), 98)
+        self._check(self.lib.pf_batch_face_draw(self.b, int(rows), _ptr(sc), C.byref(st), _ptr(int(d_base)) if d_base else None,
+                                                _ptr(int(d_out)), _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE), "pf_batch_face_draw")
 
     def encode_jpeg(self, images, **kw):
         """``Engine.encode_jpeg`` on lane 0's engine."""

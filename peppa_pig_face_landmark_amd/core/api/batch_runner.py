@@ -20,7 +20,8 @@ from ...logger.logger import logger
 from ...graph.detector import build_detector_program
 from ...graph.student import build_student_program
 from ..smoother.lk import EmaFilter
-from .facer import _box_iou, _load_weights, attach_masks, get_cfg, jpeg_chips, jpeg_options, jpeg_redacted, stage_options
+from .facer import (_box_iou, _load_weights, attach_masks, draw_options, draw_overlay, get_cfg, jpeg_chips, jpeg_options, jpeg_redacted,
+                    stage_options)
 from .hip_model_base import _RANGE_ERR
 
 
@@ -28,8 +29,12 @@ class FrameBatchRunner:
     def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, lanes: int = 3, frames_per_lane: int = 32,
                  device: Optional[int] = None, library: Optional[str] = None, graph: bool = True, top_k: Optional[int] = None,
                  face_attributes: Optional[bool] = None, face_chips: Optional[int] = None,
-                 face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None):
-        """``jpeg`` (default: ``Engine.jpeg`` of the configuration if present, else off): the option of ``FaceAna``;
+                 face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None, draw=None):
+        """``draw`` (default: ``Engine.draw`` of Skps.yml, off): the dict of ``FaceAna``; ``last_drawn`` (uint8 [F,H,W,3]) keeps the
+        frames of the last ``run`` with the faces the results carry drawn on, each lane drawing the frames it ran, and
+        ``last_drawn_jpeg`` (one ``bytes`` per frame) their files with ``jpeg`` on.
+
+        ``jpeg`` (default: ``Engine.jpeg`` of the configuration if present, else off): the option of ``FaceAna``;
         ``last_redacted_jpeg`` (one ``bytes`` per frame of the last ``run``) and ``"chip_jpeg"`` in every result dict, encoded on the
         GPU (lane 0, behind a synchronisation of the lanes); ``"raw": False`` drops ``last_redacted`` and ``"chip"``.
 
@@ -52,6 +57,8 @@ class FrameBatchRunner:
         self.last_redacted = None
         self.jpeg = jpeg_options(jpeg, eng_cfg)
         self.last_redacted_jpeg = None
+        self.draw = draw_options(draw, eng_cfg, self.redact)
+        self.last_drawn = self.last_drawn_jpeg = None
         self.device = int(eng_cfg.get("device", 0)) if device is None else int(device)
         self.dtype = eng_cfg.get("dtype", "f32s")
         root = pathlib.Path(__file__).resolve().parents[2]
@@ -136,6 +143,9 @@ class FrameBatchRunner:
         if self.jpeg and chips is not None:
             files = jpeg_chips(self.engine, self.jpeg, F * K, self.face_chips, chips[2], sync=self.engine.sync)
             chip_jpeg = [files[f * K:(f + 1) * K] for f in range(F)]
+        if self.draw:
+            self._over = draw_overlay(self.engine, self.draw, self.jpeg, self.redact, F * K, frames.shape, r[3].reshape(-1, 98),
+                                      sync=self.engine.sync)
         return r + (attrs, chips, masks, redacted, red_jpeg, chip_jpeg)
 
     def _returned_boxes(self, det_boxes: np.ndarray, kps: np.ndarray) -> np.ndarray:
@@ -158,12 +168,13 @@ class FrameBatchRunner:
         frames = np.stack(frames) if isinstance(frames, (list, tuple)) else np.asarray(frames)
         out: List[List[Dict[str, np.ndarray]]] = []
         all_labels, all_owners, all_redacted, all_red_jpeg = [], [], [], []
+        all_drawn, all_drawn_jpeg = [], []
         raw = not self.jpeg or self.jpeg["raw"]
         for s in range(0, frames.shape[0], self.max_frames):
             chunk = frames[s:s + self.max_frames]
             attrs = chips = masks = redacted = red_jpeg = chip_jpeg = None
             planted = self._planted_rows(chunk) if self._planted_rows is not None else None
-            if self.face_attributes or self.face_chips or self.face_masks or self.redact:
+            if self.face_attributes or self.face_chips or self.face_masks or self.redact or self.draw:
                 if chunk.ndim != 4 or chunk.shape[-1] != 3 or chunk.dtype != np.uint8:
                     raise ValueError("frames must be uint8 [F,H,W,3]")
                 counts, boxes, kps, scores, attrs, chips, masks, redacted, red_jpeg, chip_jpeg = self._guarded(self._run_with_extras, chunk, planted)
@@ -190,6 +201,11 @@ class FrameBatchRunner:
                 out.append(res)
             if masks is not None:
                 all_labels.append(masks[0]); all_owners.append(masks[1])
+            if self.draw:
+                if self._over[0] is not None:
+                    all_drawn.append(self._over[0])
+                if self._over[1] is not None:
+                    all_drawn_jpeg += self._over[1]
             if redacted is not None:
                 all_redacted.append(redacted)
             if red_jpeg is not None:
@@ -200,6 +216,10 @@ class FrameBatchRunner:
             self.last_redacted = np.concatenate(all_redacted)
         if all_red_jpeg:
             self.last_redacted_jpeg = all_red_jpeg
+        if all_drawn:
+            self.last_drawn = np.concatenate(all_drawn)
+        if all_drawn_jpeg:
+            self.last_drawn_jpeg = all_drawn_jpeg
         return out
 
     def close(self):

@@ -153,6 +153,65 @@ def jpeg_chips(engine, jpeg, rows, S, valid, source=None, sync=None):
     return [f if v else None for f, v in zip(files, np.asarray(valid).reshape(-1))]
 
 
+def draw_options(value, eng_cfg, redact):
+    """The ``draw`` option of the classes: ``None`` -> ``Engine.draw`` of Skps.yml; a false value is off (``None`` is returned); a
+    dict gives any of the keywords of ``Engine.draw_faces`` ("what", "point_radius", "line_width", "alpha", "score_thres",
+    "colour_hi", "colour_lo", "colour_contour", "colour_box") over its defaults, plus "base": "frame" (the default) or "redacted"
+    (draw over the redaction, which needs ``redact`` -- the options redact_options returned -- on); ``True`` is the defaults."""
+    if value is None:
+        value = eng_cfg.get("draw", None)
+    if not value:
+        return None
+    opts = {"what": ("points",), "point_radius": 2, "line_width": 1, "alpha": 256, "score_thres": 0.8, "colour_hi": (255, 255, 255),
+            "colour_lo": (0, 0, 255), "colour_contour": (0, 255, 0), "colour_box": (255, 255, 0), "base": "frame"}
+    if isinstance(value, dict):
+        unknown = set(value) - set(opts)
+        if unknown:
+            raise ValueError("draw: unknown keys %s" % sorted(unknown))
+        opts.update(value)
+    if opts["base"] not in ("frame", "redacted"):
+        raise ValueError("draw: base must be 'frame' or 'redacted' (got %r)" % (opts["base"],))
+    if opts["base"] == "redacted" and not redact:
+        raise ValueError("draw: base 'redacted' needs the redact option on")
+    _native._draw_style(**{k: v for k, v in opts.items() if k != "base"})      # a wrong name in "what" is refused here, not at the first frame
+    return opts
+
+
+def draw_overlay(engine, draw, jpeg, redact, rows, shape, scores, source=None, sync=None):
+    """The frames [F,H,W,3] (``shape``) with the faces drawn on, on the device: pf_face_draw of the last call's first ``rows`` rows,
+    or -- ``source = (frames argument, landmarks)`` -- pf_draw_faces; ``scores`` [rows,98] or None.  With "base": "redacted" the
+    redaction (``redact``) is written to device memory the engine keeps and drawn over.  Returns (the raw frames or None when
+    ``jpeg`` has "raw": False, the JPEG files or None without ``jpeg``): the files are encoded from the device output, so only they
+    cross PCIe.  ``sync``: called in front of the encoder where it runs on another stream (BatchEngine)."""
+    F, H, W = (int(v) for v in shape[:3])
+    style = {k: v for k, v in draw.items() if k != "base"}
+    d_base = 0
+    if draw["base"] == "redacted":
+        d_base = engine.device_buffer("draw_base", F * H * W * 3)
+        if source is None:
+            engine.face_redact_device(rows, d_base, **redact)
+        else:
+            engine.redact_faces_device(source[0], source[1], d_base, **redact)
+    frames = (d_base, F, H, W) if d_base and source is not None else (source[0] if source is not None else None)
+    sc = None if scores is None else np.ascontiguousarray(scores, np.float32)
+    drawn = files = None
+    if not jpeg or jpeg["raw"]:
+        if source is None:
+            drawn = engine.face_draw(rows, scores=sc, base=d_base, **style)[0]
+        else:
+            drawn = engine.draw_faces(frames, source[1], scores=sc, **style)[0]
+    if jpeg:
+        d = engine.device_buffer("jpeg_drawn", F * H * W * 3)
+        if source is None:
+            engine.face_draw_device(rows, d, scores=sc, d_base=d_base, **style)
+        else:
+            engine.draw_faces_device(frames, source[1], d, scores=sc, **style)
+        if sync is not None:
+            sync()
+        files = engine.encode_jpeg((d, F, H, W), quality=jpeg["quality"], subsampling=jpeg["subsampling"])
+    return drawn, files
+
+
 def stage_options(eng_cfg, face_attributes=None, face_chips=None, face_masks=None, redact=None):
     """The four options FaceAna, StreamTracker and FrameBatchRunner share, each from its argument or, when that is ``None``, from
     ``Engine`` of Skps.yml: (face_attributes bool, face_chips int (0 = off), face_masks bool, redact dict or None)."""
@@ -170,8 +229,16 @@ def host_frame(image) -> np.ndarray:
 class FaceAna:
     def __init__(self, verbose: bool = False, cfg: Optional[dict] = None, weights: Optional[dict] = None,
                  device: Optional[int] = None, library: Optional[str] = None, face_attributes: Optional[bool] = None,
-                 face_chips: Optional[int] = None, face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None):
-        """``jpeg`` (default: ``Engine.jpeg`` of the configuration if present, else off): a quality, or a dict with any of
+                 face_chips: Optional[int] = None, face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None, draw=None):
+        """``draw`` (default: ``Engine.draw`` of Skps.yml, off): a dict with any of the keywords of ``Engine.draw_faces`` --
+        ``"what"`` (names out of "points", "contours", "box"; default the points), ``"point_radius"``, ``"line_width"``, ``"alpha"``,
+        ``"score_thres"`` and the four colours -- and ``"base"`` ("frame", or "redacted" to draw over the redaction, which needs
+        ``redact`` on) keeps ``last_drawn`` (uint8 [H,W,3]): the frame with the landmarks, contours and boxes of every face the
+        result carries drawn on the GPU, a point white where its score exceeds the threshold and red elsewhere like the reference's
+        demo; a frame without a face comes back as a copy.  With ``jpeg`` on it also keeps ``last_drawn_jpeg`` (bytes), encoded on
+        the GPU from the device output of the overlay, and ``"raw": False`` drops ``last_drawn``.  The result dicts are unchanged.
+
+        ``jpeg`` (default: ``Engine.jpeg`` of the configuration if present, else off): a quality, or a dict with any of
         ``"quality"`` (90), ``"subsampling"`` (420, 422 or 444) and ``"raw"`` (True).  With ``redact`` on it keeps
         ``last_redacted_jpeg`` (bytes: the frame ``last_redacted`` holds as a baseline JPEG file); with ``face_chips`` on every result
         gets ``"chip_jpeg"`` (bytes, ``None`` for a degenerate fit).  Both are encoded on the GPU from the device outputs of the
@@ -223,6 +290,8 @@ class FaceAna:
         self.last_redacted = None
         self.jpeg = jpeg_options(jpeg, eng_cfg)
         self.last_redacted_jpeg = None
+        self.draw = draw_options(draw, eng_cfg, self.redact)
+        self.last_drawn = self.last_drawn_jpeg = None
         self._planted_rows = None    # test instrument: callable returning decoded detector rows that replace the detector's own
         self._det_cfg = sk["Detect"]
         self.top_k = sk["Detect"]["topk"]
@@ -255,9 +324,11 @@ class FaceAna:
                 chips = self.engine.face_chips(n, self.face_chips) if self.face_chips and n else None
                 jp = (jpeg_redacted(self.engine, self.jpeg, self.redact, n, (1,) + tuple(image.shape[:2])) if self.jpeg and self.redact and n else None,
                       jpeg_chips(self.engine, self.jpeg, n, self.face_chips, chips[2]) if self.jpeg and chips is not None else None)
+                over = (draw_overlay(self.engine, self.draw, self.jpeg, self.redact, n, (1,) + tuple(image.shape[:2]), r[2])
+                        if self.draw and n else None)
                 return r + (self.engine.face_attrs(n) if self.face_attributes else None, chips,
                             self.engine.face_masks(n) if self.face_masks and n else None,
-                            self.engine.face_redact(n, **self.redact)[0] if self.redact and n and self._raw else None, jp)
+                            self.engine.face_redact(n, **self.redact)[0] if self.redact and n and self._raw else None, jp, over)
             out = run_guarded(
                 [self.face_detector.model, self.face_landmark.model], fn, image, float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]),
                 float(self.min_face), int(self.top_k), float(self.iou_thres), float(self.alpha), float(self.diff_thres),
@@ -266,6 +337,7 @@ class FaceAna:
             self.previous_image = image
             self.track_box = boxes
             self._keep_redacted(out[7], image, out[8][0])
+            self._keep_drawn(out[9], image)
             return self.to_dict(boxes, kps, scores, out[4], out[5], self._keep_masks(out[6], image), out[8][1], self._raw)
         diff = self.engine.set_frame(image)
         self.previous_image = image
@@ -303,6 +375,11 @@ class FaceAna:
                 red_jpeg = jpeg_redacted(self.engine, self.jpeg, self.redact, len(landmarks), (1,) + tuple(image.shape[:2]),
                                          source=(None, np.asarray(landmarks)[None]))
         self._keep_redacted(redacted, image, red_jpeg)
+        over = None
+        if self.draw and len(landmarks):            # on the resident frame, with the smoothed landmarks and the scores the result carries
+            over = draw_overlay(self.engine, self.draw, self.jpeg, self.redact, len(landmarks), (1,) + tuple(image.shape[:2]),
+                                np.asarray(states), source=(None, np.asarray(landmarks)[None]))
+        self._keep_drawn(over, image)
         return self.to_dict(self.track_box, landmarks, states, attrs, chips, self._keep_masks(masks, image), chip_jpeg, self._raw)
 
     @property
@@ -317,6 +394,18 @@ class FaceAna:
             self.last_redacted = host_frame(image) if redacted is None else redacted[0]
         if self.redact and self.jpeg:
             self.last_redacted_jpeg = red_jpeg[0] if red_jpeg is not None else self.engine.encode_jpeg(
+                image if isinstance(image, _native.DeviceFrame) else np.asarray(image), quality=self.jpeg["quality"],
+                subsampling=self.jpeg["subsampling"])[0]
+
+    def _keep_drawn(self, over, image):
+        """(frames [1,H,W,3] or None, files or None) of draw_overlay, or None when the frame has no face (the frame itself is kept
+        and encoded) -> last_drawn, last_drawn_jpeg."""
+        if not self.draw:
+            return
+        if self._raw:
+            self.last_drawn = host_frame(image) if over is None else over[0][0]
+        if self.jpeg:
+            self.last_drawn_jpeg = over[1][0] if over is not None else self.engine.encode_jpeg(
                 image if isinstance(image, _native.DeviceFrame) else np.asarray(image), quality=self.jpeg["quality"],
                 subsampling=self.jpeg["subsampling"])[0]
 

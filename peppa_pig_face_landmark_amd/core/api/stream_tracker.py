@@ -16,7 +16,7 @@ import numpy as np
 
 from ... import _native
 from ...logger.logger import logger
-from .facer import FaceAna, _load_weights, get_cfg, jpeg_chips, jpeg_options, jpeg_redacted, stage_options
+from .facer import FaceAna, _load_weights, draw_options, draw_overlay, get_cfg, jpeg_chips, jpeg_options, jpeg_redacted, stage_options
 from .hip_model_base import HIPEngine, run_guarded
 
 
@@ -24,8 +24,12 @@ class StreamTracker:
     def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, max_streams: int = 8,
                  device: Optional[int] = None, library: Optional[str] = None, verbose: bool = False,
                  face_attributes: Optional[bool] = None, face_chips: Optional[int] = None,
-                 face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None):
-        """``jpeg`` (default: ``Engine.jpeg`` of the configuration if present, else off): the option of ``FaceAna``;
+                 face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None, draw=None):
+        """``draw`` (default: ``Engine.draw`` of Skps.yml, off): the dict of ``FaceAna``; ``last_drawn`` (stream id -> uint8 [H,W,3])
+        keeps the frames of the last call with the faces the results carry drawn on, ``last_drawn_jpeg`` (stream id -> bytes) their
+        files with ``jpeg`` on.
+
+        ``jpeg`` (default: ``Engine.jpeg`` of the configuration if present, else off): the option of ``FaceAna``;
         ``last_redacted_jpeg`` (stream id -> bytes) and ``"chip_jpeg"`` in every result dict, encoded on the GPU; ``"raw": False``
         drops ``last_redacted`` and ``"chip"``.
 
@@ -60,6 +64,9 @@ class StreamTracker:
         self.last_redacted: Optional[Dict[int, np.ndarray]] = None
         self.jpeg = jpeg_options(jpeg, eng_cfg)
         self.last_redacted_jpeg: Optional[Dict[int, bytes]] = None
+        self.draw = draw_options(draw, eng_cfg, self.redact)
+        self.last_drawn: Optional[Dict[int, np.ndarray]] = None
+        self.last_drawn_jpeg: Optional[Dict[int, bytes]] = None
         self.last_label_maps: Dict[int, np.ndarray] = {}
         self.last_owner_maps: Dict[int, np.ndarray] = {}
         self.max_streams = int(max_streams)
@@ -90,10 +97,17 @@ class StreamTracker:
         planted = self._planted_rows(ids, batch) if self._planted_rows is not None else None
         K = self.top_k
 
+        over = [None, None]
+
         def call(*args):
             r = self.engine.track_streams(*args)
             attrs = chips = masks = redacted = red_jpeg = chip_jpeg = None
             raw = not self.jpeg or self.jpeg["raw"]
+            if self.draw:                              # the scores of the call's [n][top_k] rows, compacted like kps
+                sc = np.zeros((len(r), K, 98), np.float32)
+                for i, (b, _, s_i, _) in enumerate(r):
+                    sc[i, :len(b)] = s_i
+                over[:] = draw_overlay(self.engine, self.draw, self.jpeg, self.redact, len(r) * K, batch.shape, sc.reshape(-1, 98))
             if self.redact and raw:
                 redacted = self.engine.face_redact(len(r) * K, **self.redact)[0]      # one frame per listed stream
             if self.redact and self.jpeg:
@@ -119,6 +133,10 @@ class StreamTracker:
             self.last_redacted = {s: redacted[i] for i, s in enumerate(ids)}
         if red_jpeg is not None:
             self.last_redacted_jpeg = {s: red_jpeg[i] for i, s in enumerate(ids)}
+        if over[0] is not None:
+            self.last_drawn = {s: over[0][i] for i, s in enumerate(ids)}
+        if over[1] is not None:
+            self.last_drawn_jpeg = {s: over[1][i] for i, s in enumerate(ids)}
         if masks is not None:
             self.last_label_maps = {s: m[0] for s, m in zip(ids, masks)}
             self.last_owner_maps = {s: m[1] for s, m in zip(ids, masks)}

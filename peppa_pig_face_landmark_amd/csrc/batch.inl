@@ -396,4 +396,23 @@ int pf_batch_face_redact(pf_batch* b, int rows, const int* select, int mode, int
     });
 }
 
+/* pf_face_draw of the lanes, gathered the same way: lane i draws the frames it ran, base and out offset alike */
+int pf_batch_face_draw(pf_batch* b, int rows, const float* scores, const pf_draw_style* style, const uint8_t* base, uint8_t* out, int* valid,
+                       int out_mem) {
+    if (!b) return 1;
+    char buf[200];
+    if (const char* why = draw_check(style, out, buf, sizeof(buf))) PF_BFAIL(b, "pf_batch_face_draw: %s", why);
+    if (!face_out_mem_ok(out_mem)) PF_BFAIL(b, "pf_batch_face_draw: bad out_mem %d", out_mem);
+    if (batch_rows_check(b, "pf_batch_face_draw", "face rows", rows)) return 1;
+    if (rows == 0) return 0;
+    int F = 0, H = 0, W = 0;
+    if (pf_batch_face_masks_shape(b, rows, &F, &H, &W)) return 1;
+    const size_t frame_bytes = (size_t)H * W * 3;
+    if (base && out_mem == PF_MEM_DEVICE && draw_overlap(base, out, (size_t)F * frame_bytes)) PF_BFAIL(b, "pf_batch_face_draw: base must not alias out");
+    return batch_lanes(b, "pf_batch_face_draw", "face rows", rows, true, [&](pf_handle* h, int f0, int r0, int nr) {
+        return pf_face_draw(h, nr, scores ? scores + (size_t)r0 * PF_DRAW_NPOINTS : nullptr, style, base ? base + (size_t)f0 * frame_bytes : nullptr,
+                            out + (size_t)f0 * frame_bytes, valid ? valid + r0 : nullptr, out_mem);
+    });
+}
+
 }  // extern "C"

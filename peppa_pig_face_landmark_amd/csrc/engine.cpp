@@ -38,6 +38,7 @@
 #include "k_align.h"
 #include "k_mask.h"
 #include "k_redact.h"
+#include "k_draw.h"
 #include "face_rows.h"
 #include "pf_program.h"
 
@@ -131,6 +132,7 @@ struct pf_handle {
     MaskState mask;          // face-region label maps (mask.inl): scratch of its two kernels
     // face redaction (redact.inl): the label maps it reads and the staging of host outputs
     RedactState redact;
+    DrawState draw;          // face overlay (draw.inl): the primitives of its two kernels and the staging of host outputs
     // profiling
     bool profiling = false;
     std::map<std::string, ProfEntry> prof;
@@ -454,6 +456,7 @@ int pf_create(int device_id, pf_handle** out) {
         if (const char* v = getenv("PEPPA_ALIGN_LDS")) h->align.lds_budget = atoi(v);     // 0: every align_warp tile takes the direct path (tools/bench_face_chips.py)
         if (const char* v = getenv("PEPPA_MASK_NOCULL")) h->mask.no_cull = atoi(v) ? 1 : 0;       // 1: mask_fill evaluates every slot in every tile, no parity folding (tools/bench_face_masks.py)
         if (const char* v = getenv("PEPPA_REDACT_STAGE_ALL")) h->redact.stage_all = atoi(v) ? 1 : 0;       // 1: redact_kernel stages every tile through LDS, none is copied (tools/bench_face_redact.py)
+        if (const char* v = getenv("PEPPA_DRAW_NOCULL")) h->draw.no_cull = atoi(v) ? 1 : 0;       // 1: draw_kernel stages every tile and lists every primitive of the image in it (tools/bench_face_draw.py)
         if (const char* v = getenv("PEPPA_DET_TILE")) { if (sscanf(v, "%d,%d", &g_det_tile_th, &g_det_tile_tw) != 2) g_det_tile_th = g_det_tile_tw = 0; }
     }
     bool masked = false;
@@ -507,6 +510,7 @@ void pf_destroy(pf_handle* h) {
     h->align.release();
     h->mask.release();
     h->redact.release();
+    h->draw.release();
     h->track.release();
     h->streams.release();
     h->jpeg.release();
@@ -756,6 +760,7 @@ int pf_profile_fetch(pf_handle* h, char* names, size_t names_cap, float* ms, int
 #include "align.inl"
 #include "mask.inl"
 #include "redact.inl"
+#include "draw.inl"
 #include "pipeline.inl"
 #include "comm.inl"
 #include "track.inl"

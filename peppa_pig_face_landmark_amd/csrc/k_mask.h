@@ -77,6 +77,20 @@ __device__ __forceinline__ long long pf_mask_ceil_div(long long n, long long d) 
     return q + (r > 0 ? 1 : 0);
 }
 
+// What mask_edges_kernel and draw_prims_kernel (k_draw.h) share, so that a slot is live and boxed alike for the maps and the overlay.
+// A slot is live iff it lies below its frame's count and its flag of the last call, where either is given.
+__device__ __forceinline__ int pf_mask_live(const int* counts, int per_frame, const int* valid_in, int valid_stride, int slot) {
+    if (counts && (slot % per_frame) >= counts[slot / per_frame]) return 0;
+    if (valid_in && valid_in[(size_t)slot * valid_stride] == 0) return 0;
+    return 1;
+}
+
+// the clipped box of a slot from the Q4 extremes of its vertices 0..95: pixels x0 <= x < x1, y0 <= y < y1 inside [0, W] x [0, H]
+__device__ __forceinline__ void pf_mask_box(int X0, int Y0, int X1, int Y1, int W, int H, int* box) {
+    box[0] = min(max(pf_mask_ceil16(X0), 0), W); box[1] = min(max(pf_mask_ceil16(Y0), 0), H);
+    box[2] = min(max(pf_mask_ceil16(X1), 0), W); box[3] = min(max(pf_mask_ceil16(Y1), 0), H);
+}
+
 struct MaskEdgesArgs {
     const void* kps;          // [n][98][2] float32 or float64
     int kps_f64;
@@ -100,9 +114,7 @@ __global__ __launch_bounds__(64) void mask_edges_kernel(MaskEdgesArgs a) {
     __shared__ int s_ok;
     const int t = threadIdx.x, slot = blockIdx.x;
     int* rec = a.rec + (size_t)slot * PF_MASK_REC;
-    int live = 1;                                                // the same in every lane
-    if (a.counts && (slot % a.per_frame) >= a.counts[slot / a.per_frame]) live = 0;
-    if (live && a.valid_in && a.valid_in[(size_t)slot * a.valid_stride] == 0) live = 0;
+    const int live = pf_mask_live(a.counts, a.per_frame, a.valid_in, a.valid_stride, slot);      // the same in every lane
     double x[2] = {0.0, 0.0}, y[2] = {0.0, 0.0};
     int fin = 1;
     if (live) {
@@ -153,8 +165,8 @@ __global__ __launch_bounds__(64) void mask_edges_kernel(MaskEdgesArgs a) {
             x0 = min(x0, s_xy[v][0]); x1 = max(x1, s_xy[v][0]);
             y0 = min(y0, s_xy[v][1]); y1 = max(y1, s_xy[v][1]);
         }
-        const int box[4] = {min(max(pf_mask_ceil16(x0), 0), a.W), min(max(pf_mask_ceil16(y0), 0), a.H),
-                            min(max(pf_mask_ceil16(x1), 0), a.W), min(max(pf_mask_ceil16(y1), 0), a.H)};
+        int box[4];
+        pf_mask_box(x0, y0, x1, y1, a.W, a.H, box);
         rec[0] = 1;
         for (int i = 0; i < 4; ++i) {
             rec[1 + i] = box[i];

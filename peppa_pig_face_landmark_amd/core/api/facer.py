@@ -484,7 +484,9 @@ class FaceAna:
         keep = area > self.min_face
         area, bboxes = area[keep], bboxes[keep, :]
         if bboxes.shape[0] > self.top_k:
-            bboxes = bboxes[area.argsort()[-self.top_k:][::-1]]
+            # equal areas: the later row first, as the reference's argsort gives under its pinned numpy (an insertion sort at
+            # these sizes) and as track_select_kernel does; newer numpy sorts float32 with SIMD networks that keep no order
+            bboxes = bboxes[area.argsort(kind="stable")[-self.top_k:][::-1]]
         return np.array(bboxes)
 
     def judge_boxs(self, previuous_bboxs, now_bboxs):

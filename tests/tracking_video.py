@@ -86,3 +86,96 @@ def video_long():
         rows = [plant_rows(b, hw, 15120, (384, 640), 6, seed=40 + i) for i, (_, b) in enumerate(seg)]
         out.append((frames, rows, hw))
     return out
+
+
+# ---- the edge video: every decision of the tracker at its boundary, on a frame whose byte count is no multiple of 16 ----------
+GOLDEN_EDGES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tracking_video_edges.npz")
+HW_EDGES = (271, 483)       # 271 * 483 * 3 = 392679 = 16 * 24542 + 7: the stream gate takes its byte loop for the tail
+
+
+def _planted(faces_per_frame, seed0, hw=HW_EDGES):
+    rows = []
+    for i, faces in enumerate(faces_per_frame):
+        b = np.asarray([[cx - fw / 2, cy - fh / 2, cx + fw / 2, cy + fh / 2] for cx, cy, fw, fh in faces], np.float32).reshape(-1, 4)
+        rows.append(plant_rows(b, hw, 15120, (384, 640), 6, seed=seed0 + i))
+    return rows
+
+
+def nms_boxes(rows, hw=HW_EDGES):
+    """What the reference's detector stage returns for planted rows (numpy restatement: xywh2xyxy, py_nms, scale_coords)."""
+    from oracle import prepost as pp
+    s, _, _, top, _, left, _ = pp.letterbox_geometry(hw[0], hw[1], (384, 640))
+    return pp.detector_postprocess(rows, [s, left, top], 0.3, 0.5)
+
+
+def video_edges():
+    """22 frames of 271 x 483 in seven segments with reset() between them, each named after the decision it puts on its
+    boundary.  Conventions of video_long(): scene() frames, plant_rows() rows for the 384 x 640 detector, S_LONG crops with
+    long_video_weights, top_k = 5, face widths that are no multiple of 5 (see video_long: 1.4 * w).  A segment is a dict:
+    name, group ("A": the reference itself runs it; "B": the reference raises, the engine's documented behaviour decides),
+    frames, rows, faces (the planted (cx, cy, w, h) per frame), hw, min_face, and expect -- hand-stated counts, detector_ran
+    and, per frame, which planted face each output row is.  NMS returns the planted boxes in REVERSE planting order (the
+    k-th planted box scores 0.99 + 0.0005 k), which is what "earlier / later row" refers to below.
+
+    gate_equal       f, f + 5 on every byte (mean difference exactly 5.0: `diff > 5` is false, the detector is skipped),
+                     that + 5 with one byte + 6 (sum 5 N + 1: it runs), that - 5 with one byte - 4 (5 N - 1: skipped).
+    min_face_equal   min_face is the float32 area NMS returns for the first planted face (46 x 58 at x = 62: 2667.99976,
+                     one ulp under 2668); the same face at x = 160 comes back as 2668.0.  Strict `>` drops the first only.
+    equal_areas      seven faces; the 5th and 6th by area (58 x 76 at x = 60 and x = 180) come back with bit-equal float32
+                     areas (4408.0).  top_k = 5 keeps one: the later row (x = 60), as the reversed ascending argsort does.
+    iou_first        two flat faces 19 px apart (box IoU 0.26, under the NMS threshold) whose landmark hulls and track
+                     boxes overlap heavily; two gated repeats give GroupTrack two previous hulls above 0.5 for one face, then a
+                     detector frame plants one face on the SECOND track box: its IoU with both exceeds 0.5, the first wins.
+    one_euro         a 26 x 36 face (min_face 300) and a gated repeat: one of its 98 points moves less than 0.002 of the
+                     frame (al = 0.01), the others more.  With the random-weight Student every crop change moves almost
+                     every point, so frozen points are rare; this layout has one.
+    empty            three faces, a changed frame with no row above the score threshold (detector runs, zero faces, the
+                     track stays -- empty), the same frame twice (gate closed, zero faces), a changed frame with three faces.
+    rejected_crop    (B) six faces, five selected by area; the third of them is 18 x 130 (area 2340 > min_face, width <= 20),
+                     which the landmark stage rejects: four rows come back, the two after it one row up, and stay so on two
+                     gated repeats.  The reference dereferences None there (face_landmark.py:76-77, :44)."""
+    h, w = HW_EDGES
+    segs = []
+
+    def seg(name, group, faces, seeds, seed0, min_face, expect, frames=None):
+        fr = frames if frames is not None else [scene(h, w, f, s)[0] for f, s in zip(faces, seeds)]
+        segs.append(dict(name=name, group=group, frames=fr, rows=_planted(faces, seed0), faces=faces, hw=(h, w),
+                         min_face=float(min_face), expect=expect))
+
+    # gate_equal
+    two = [(120, 100, 52, 68), (330, 150, 64, 84)]
+    f0 = np.minimum(scene(h, w, two, 71)[0], 240)
+    f1 = f0 + 5
+    f2 = f1 + 5
+    f2[0, 0, 0] += 1
+    f3 = f2 - 5
+    f3[h - 1, w - 1, 2] += 1                                   # the last byte of the frame: the tail of the byte loop
+    seg("gate_equal", "A", [two] * 4, None, 400, 1600, dict(counts=[2, 2, 2, 2], detector_ran=[1, 0, 1, 0], row_face=[[1, 0]] * 4),
+        frames=[f0, f1, f2, f3])
+    # min_face_equal
+    mf = [(62, 100, 46, 58), (160, 100, 46, 58), (330, 150, 64, 84)]
+    min_face = nms_boxes(_planted([mf], 410)[0])[2]      # the first planted face is the last NMS row
+    min_face = np.float32(min_face[2] - min_face[0]) * np.float32(min_face[3] - min_face[1])
+    seg("min_face_equal", "A", [mf] * 2, [72, 72], 410, min_face, dict(counts=[2, 2], detector_ran=[1, 0], row_face=[[2, 1]] * 2))
+    # equal_areas
+    seven = [(60, 70, 58, 76), (180, 70, 58, 76), (300, 70, 66, 86), (420, 70, 74, 96),
+             (60, 200, 82, 106), (190, 200, 51, 66), (320, 200, 91, 116)]
+    seg("equal_areas", "A", [seven] * 2, [73, 73], 420, 1600, dict(counts=[5, 5], detector_ran=[1, 0], row_face=[[6, 4, 3, 2, 0]] * 2))
+    # iou_first
+    pair = [(240, 120, 52, 32), (240, 139, 52, 32)]
+    between = [(237.5, 134, 81, 82)]
+    seg("iou_first", "A", [pair, pair, pair, between], [61, 61, 61, 74], 430, 1200,
+        dict(counts=[2, 2, 2, 1], detector_ran=[1, 0, 0, 1], row_face=[[1, 0]] * 3 + [[0]]))
+    # one_euro
+    tiny = [(222, 130, 26, 36)]
+    seg("one_euro", "A", [tiny] * 2, [62, 62], 440, 300, dict(counts=[1, 1], detector_ran=[1, 0], row_face=[[0]] * 2))
+    # empty
+    three = [(90, 90, 52, 68), (240, 170, 64, 84), (400, 100, 58, 76)]
+    moved = [(96, 96, 52, 68), (246, 164, 64, 84), (394, 106, 58, 76)]
+    seg("empty", "A", [three, [], [], [], moved], [75, 76, 76, 76, 77], 450, 1600,
+        dict(counts=[3, 0, 0, 0, 3], detector_ran=[1, 1, 0, 0, 1], row_face=[[2, 1, 0], [], [], [], [2, 1, 0]]))
+    # rejected_crop
+    six = [(70, 75, 91, 116), (200, 70, 74, 96), (300, 80, 18, 130), (390, 60, 42, 52), (120, 210, 38, 49), (280, 215, 34, 50)]
+    seg("rejected_crop", "B", [six] * 3, [78, 78, 78], 460, 1600,
+        dict(counts=[4, 4, 4], detector_ran=[1, 0, 0], row_face=[[0, 1, 3, 4]] * 3, n_sel=5, n_valid=4))
+    return segs

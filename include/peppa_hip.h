@@ -427,6 +427,49 @@ int pf_track_streams(pf_handle* h, int n, const int* stream_ids, const uint8_t* 
 /* FaceAna.reset() of one stream (stream_id >= 0) or of all (-1). */
 int pf_track_streams_reset(pf_handle* h, int stream_id);
 
+/* Persistent face ids (kernel track_ident_kernel, csrc/k_track.h): which row of frame t is which row of frame
+ * t - 1, as an integer id per output row of pf_track_frame* / pf_track_streams.  Off unless pf_track_ids_config switches it on; the
+ * results of the tracking calls are bit-identical either way and the calls gain no synchronisation.  The rule is exact and integer.
+ * State per stream, on the device: id[r] and age[r] for the rows r of the track boxes (row r of the previous call's output is row r
+ * of the track boxes); a counter next_id (the first id is 1, 0 means "no id"); a lost list of at most 64 entries in insertion order,
+ * each (id, age, box[4] float64, gone).  Per frame of a stream, with keep_lost in [0, 255]:
+ *   1. Source of a selected row.  On a detector frame the source of selected row q is the previous row j that judge_boxs smoothed
+ *      its detection with: the first j with IoU > track_iou_thres; no source if there was no match or no track.  The weight w of the
+ *      claim is that IoU, as the judge computed it in that frame's dtype, held as a double.  On a gated (non-detector) frame selected
+ *      row q is row k of the track boxes: its source is k, and no two rows can share it.  A previous row whose id is 0 passes on no
+ *      source.
+ *   2. Output rows are the selected rows the landmark stage accepted, compacted in order.
+ *   3. Conflicts.  If several output rows have the same source j, the one with the greatest w keeps it; on equal w the lowest output
+ *      row keeps it.  The others have no source.
+ *   4. A row with source j gets id = id_prev[j] and age = age_prev[j] + 1.
+ *   5. Rows without a source, in ascending output-row order.  If keep_lost > 0, the row's new track box (its row of the track boxes
+ *      after this frame's hull judge, stored as float64) is compared with the box of every lost entry no earlier row has claimed: the
+ *      IoU of judge_boxs in float64 with no FMA contraction.  The entry with the greatest IoU > track_iou_thres is taken, ties go to
+ *      the lowest entry index; the row gets that entry's id and age + 1, and the entry is removed.  With no such entry, or with
+ *      keep_lost == 0, the row gets id = next_id++ and age = 1.
+ *   6. Lost list update, in this order: claimed entries are removed, compacting stably; every remaining entry gets gone += 1; entries
+ *      with gone > keep_lost are dropped; every previous row with id != 0 that no output row kept is appended with its previous track
+ *      box and gone = 1, in ascending previous-row order (rows unmatched on a detector frame, filtered by min_face or top_k, rejected
+ *      by the crop stage, or the loser's source in step 3); while more than 64 entries remain, the entry with the greatest gone is
+ *      dropped, ties drop the earliest inserted.  With keep_lost == 0 the list stays empty.
+ * So a face absent from up to keep_lost consecutive frames comes back with its id.
+ * Lifetime.  pf_track_reset, pf_track_streams_reset and the range-guard reset of a failed call forget id, age and the lost list of
+ * the streams they reset and leave next_id alone: an id is never reused within the lifetime of a pool.  Reallocating a pool
+ * (pf_track_streams_config, pf_track_frame growing top_k) restarts its counters at 1.  Ids are per stream: unique across streams is
+ * (stream, id).
+ * LIMITS: geometric identity only (IoU, no appearance): two people who swap places behind an occlusion swap ids; 64 lost entries;
+ * ids for at most 64 faces per frame: with ids on, pf_track_frame* and pf_track_streams_config refuse a top_k above 64, and
+ * pf_track_ids_config refuses to switch ids on while a pool has one; each refuses before it changes anything.
+ *
+ * pf_track_ids_config: both pools of the handle (pf_track_frame's and pf_track_streams'); enabling, disabling or changing keep_lost
+ * forgets the identity state of both (ids restart at 1) and leaves the tracking state alone; keep_lost outside [0, 255] is refused.
+ * pf_track_ids: ids and ages of the rows of the handle's last tracking call, counted as pf_face_chips counts them ([n] after
+ * pf_track_frame, [n][top_k] after pf_track_streams; rows beyond a frame's count are 0); out_mem PF_MEM_HOST (the copies the call
+ * itself brought back: no device traffic) or PF_MEM_DEVICE (enqueued on the handle's stream); either pointer may be NULL.  Refused
+ * when the last call left no rows or was not a tracking call, when ids are off, or when rows exceeds what the call left. */
+int pf_track_ids_config(pf_handle* h, int enable, int keep_lost);
+int pf_track_ids(pf_handle* h, int rows, int* ids, int* ages, int out_mem);
+
 /* Frame ingest (replaces the pageable numpy arrays cv2.imread / VideoCapture.read hand to
  * FaceAna.run, demo.py:13-17,76): page-locked host memory for frame batches (decode straight into it) and for
  * results.  Frames passed with mem = PF_MEM_HOST from such a buffer are copied host->device asynchronously on the

@@ -103,6 +103,10 @@ def _declare(lib):
     lib.pf_track_streams.restype = i
     lib.pf_track_streams_reset.argtypes = [vp, i]
     lib.pf_track_streams_reset.restype = i
+    lib.pf_track_ids_config.argtypes = [vp, i, i]
+    lib.pf_track_ids_config.restype = i
+    lib.pf_track_ids.argtypes = [vp, i, vp, vp, i]
+    lib.pf_track_ids.restype = i
     lib.pf_run_frames.argtypes = [vp, vp, i, i, i, i, f, f, f, i, vp, vp, vp, vp, i]
     lib.pf_run_frames_planted.argtypes = [vp, vp, i, i, i, i, vp, i, f, f, f, i, vp, vp, vp, vp, i]
     lib.pf_letterbox.argtypes = [vp, vp, i, i, i, i, i, i, vp, fp]
@@ -1048,6 +1052,25 @@ class Engine:
 
     def track_streams_reset(self, stream_id: int = -1):
         self._check(self.lib.pf_track_streams_reset(self.h, int(stream_id)), "pf_track_streams_reset")
+
+    # ---- persistent face ids of the tracking calls (include/peppa_hip.h pf_track_ids_config / pf_track_ids) -------------------------
+    def track_ids_config(self, enable: bool, keep_lost: int = 0):
+        """Persistent ids for ``track_frame`` and ``track_streams`` on or off (off by default); ``keep_lost``: frames (0 .. 255) an
+        id that left is remembered for.  Any change forgets the ids handed out so far (they restart at 1), never the tracks."""
+        self._check(self.lib.pf_track_ids_config(self.h, 1 if enable else 0, int(keep_lost)), "pf_track_ids_config")
+
+    def track_ids(self, rows: int):
+        """(ids int32 [rows], ages int32 [rows]) of the rows of the last tracking call, counted as ``face_chips`` counts them: [n]
+        after ``track_frame``, [n * top_k] after ``track_streams`` (0 beyond a frame's count)."""
+        ids = np.zeros((int(rows),), np.int32)
+        ages = np.zeros((int(rows),), np.int32)
+        self._check(self.lib.pf_track_ids(self.h, int(rows), _ptr(ids), _ptr(ages), PF_MEM_HOST), "pf_track_ids")
+        return ids, ages
+
+    def track_ids_device(self, rows: int, d_ids: int = 0, d_ages: int = 0):
+        """Same into device memory (int32 [rows] each, 0 = not wanted), enqueued on the handle's stream."""
+        self._check(self.lib.pf_track_ids(self.h, int(rows), _ptr(int(d_ids)) if d_ids else None, _ptr(int(d_ages)) if d_ages else None,
+                                          PF_MEM_DEVICE), "pf_track_ids")
 
     def set_option(self, option: int, value: int):
         """PF_OPT_HIP_GRAPH (1): replay device-resident run_frames calls from a captured hipGraph."""

@@ -51,6 +51,7 @@ class FaceLandmark:
             kps, scores, valid, attrs = self.model.guarded(landmarks_and_attrs, img, bboxes[:, :4])
         else:
             kps, scores, valid = self.model.guarded(self.engine.landmarks, img, bboxes[:, :4])
+        self.last_valid = np.asarray(valid, bool)      # which of the boxes the crop stage accepted (persistent ids)
         dt = time.time() - t0
         logger.info("keypoints done, time consume: %.5f and %.5f per face", dt, dt / len(bboxes))
         if self.face_attributes:

@@ -18,6 +18,7 @@ import yaml
 
 from ... import _native
 from ...logger.logger import logger
+from ..smoother.ident import IdentityTracker, ids_options, spare_select
 from ..smoother.lk import EmaFilter, GroupTrack
 from .face_detector import FaceDetector
 from .face_landmark import FaceLandmark
@@ -229,8 +230,17 @@ def host_frame(image) -> np.ndarray:
 class FaceAna:
     def __init__(self, verbose: bool = False, cfg: Optional[dict] = None, weights: Optional[dict] = None,
                  device: Optional[int] = None, library: Optional[str] = None, face_attributes: Optional[bool] = None,
-                 face_chips: Optional[int] = None, face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None, draw=None):
-        """``draw`` (default: ``Engine.draw`` of Skps.yml, off): a dict with any of the keywords of ``Engine.draw_faces`` --
+                 face_chips: Optional[int] = None, face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None, draw=None,
+                 track_ids=None, spare_ids=None):
+        """``track_ids`` (default: ``Engine.track_ids`` of Skps.yml, off): ``True`` or ``{"keep_lost": n}`` gives every result dict
+        ``"id"`` (int, from 1, stable while the face is tracked; a face absent for up to ``keep_lost`` frames comes back with its id)
+        and ``"age"`` (int, frames the id has been seen), in both tracking modes (the rule: include/peppa_hip.h, "Persistent face
+        ids").  Geometric identity only (IoU, no appearance): two people who swap places behind an occlusion swap ids.  ``reset()``
+        forgets the ids but never reuses one.  ``spare_ids`` (a set of ids, needs ``track_ids`` and is read by ``redact``; may be
+        changed between calls through the attribute): a face whose id is in the set is not redacted, every other face -- one seen
+        for the first time included -- is.
+
+        ``draw`` (default: ``Engine.draw`` of Skps.yml, off): a dict with any of the keywords of ``Engine.draw_faces`` --
         ``"what"`` (names out of "points", "contours", "box"; default the points), ``"point_radius"``, ``"line_width"``, ``"alpha"``,
         ``"score_thres"`` and the four colours -- and ``"base"`` ("frame", or "redacted" to draw over the redaction, which needs
         ``redact`` on) keeps ``last_drawn`` (uint8 [H,W,3]): the frame with the landmarks, contours and boxes of every face the
@@ -292,10 +302,16 @@ class FaceAna:
         self.last_redacted_jpeg = None
         self.draw = draw_options(draw, eng_cfg, self.redact)
         self.last_drawn = self.last_drawn_jpeg = None
+        self.track_ids = ids_options(track_ids, eng_cfg)
+        if spare_ids is not None and not self.track_ids:
+            raise ValueError("spare_ids needs track_ids on")
+        self.spare_ids = set(spare_ids or ())
         self._planted_rows = None    # test instrument: callable returning decoded detector rows that replace the detector's own
         self._det_cfg = sk["Detect"]
         self.top_k = sk["Detect"]["topk"]
         self.engine = _native.Engine(dev, library)      # one GPU, one stream, shared by both stages
+        if self.track_ids and self.device_tracking:
+            self.engine.track_ids_config(True, self.track_ids["keep_lost"])
         max_faces = max(int(eng_cfg.get("max_faces", 8)), int(self.top_k))
         self.face_detector = FaceDetector(sk["Detect"], det_w, engine=self.engine, dtype=dtype)
         self.face_landmark = FaceLandmark(sk["Keypoints"], kps_w, engine=self.engine, dtype=dtype, max_batch=max_faces,
@@ -311,6 +327,25 @@ class FaceAna:
         self.iou_thres = sk["Trace"]["iou_thres"]
         self.alpha = sk["Trace"]["smooth_box"]
         self.filter = EmaFilter(self.alpha)
+        # host tracking mode: the identity rule in numpy, fed by judge_boxs and sort_and_filter
+        self._ident = IdentityTracker(self.track_ids["keep_lost"], self.iou_thres) if self.track_ids and not self.device_tracking else None
+        self._judge_src = self._sel_rows = None
+
+    def configure_track_ids(self, keep_lost: int):
+        """Another ``keep_lost`` for ``track_ids``: the ids handed out so far are forgotten (they restart at 1), the tracks stay."""
+        if not self.track_ids:
+            raise ValueError("track_ids is off")
+        self.track_ids = ids_options({"keep_lost": keep_lost}, {})
+        if self.device_tracking:
+            self.engine.track_ids_config(True, self.track_ids["keep_lost"])
+        else:
+            self._ident = IdentityTracker(self.track_ids["keep_lost"], self.iou_thres)
+
+    def _redact_with(self, ids):
+        """The redact options with the ``select`` the ids imply (``spare_ids``), or as they are without ``track_ids``."""
+        if not self.redact or ids is None:
+            return self.redact
+        return dict(self.redact, select=spare_select(ids, self.spare_ids))
 
     # ---- per-frame entry ---------------------------------------------------------------------------
     def run(self, image: np.ndarray):
@@ -321,14 +356,16 @@ class FaceAna:
             def fn(*args):       # the attribute rows / chips of the tracked faces, compacted like kps (pf_face_attrs / pf_face_chips after pf_track_frame)
                 r = self.engine.track_frame(*args)
                 n = len(r[0])
+                ids = self.engine.track_ids(n) if self.track_ids else None
+                red = self._redact_with(ids[0] if ids else None)
                 chips = self.engine.face_chips(n, self.face_chips) if self.face_chips and n else None
-                jp = (jpeg_redacted(self.engine, self.jpeg, self.redact, n, (1,) + tuple(image.shape[:2])) if self.jpeg and self.redact and n else None,
+                jp = (jpeg_redacted(self.engine, self.jpeg, red, n, (1,) + tuple(image.shape[:2])) if self.jpeg and self.redact and n else None,
                       jpeg_chips(self.engine, self.jpeg, n, self.face_chips, chips[2]) if self.jpeg and chips is not None else None)
-                over = (draw_overlay(self.engine, self.draw, self.jpeg, self.redact, n, (1,) + tuple(image.shape[:2]), r[2])
+                over = (draw_overlay(self.engine, self.draw, self.jpeg, red, n, (1,) + tuple(image.shape[:2]), r[2])
                         if self.draw and n else None)
                 return r + (self.engine.face_attrs(n) if self.face_attributes else None, chips,
                             self.engine.face_masks(n) if self.face_masks and n else None,
-                            self.engine.face_redact(n, **self.redact)[0] if self.redact and n and self._raw else None, jp, over)
+                            self.engine.face_redact(n, **red)[0] if self.redact and n and self._raw else None, jp, over, ids)
             out = run_guarded(
                 [self.face_detector.model, self.face_landmark.model], fn, image, float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]),
                 float(self.min_face), int(self.top_k), float(self.iou_thres), float(self.alpha), float(self.diff_thres),
@@ -338,7 +375,7 @@ class FaceAna:
             self.track_box = boxes
             self._keep_redacted(out[7], image, out[8][0])
             self._keep_drawn(out[9], image)
-            return self.to_dict(boxes, kps, scores, out[4], out[5], self._keep_masks(out[6], image), out[8][1], self._raw)
+            return self.with_ids(self.to_dict(boxes, kps, scores, out[4], out[5], self._keep_masks(out[6], image), out[8][1], self._raw), out[10])
         diff = self.engine.set_frame(image)
         self.previous_image = image
         if diff is None or self.track_box is None or diff > self.diff_thres:
@@ -347,6 +384,8 @@ class FaceAna:
             self.trace.previous_landmarks_set = None     # detector ran: smoothing history is dropped
         else:
             boxes = self.track_box
+            self._judge_src = [(k, 0.0) for k in range(len(boxes))]      # a gated frame: selected row q is row k of track_box
+        previous_track, judge_src = self.track_box, self._judge_src      # before the hull judge below replaces both
         boxes = self.sort_and_filter(boxes)
         boxes_return = np.array(boxes)
         attrs = None
@@ -357,6 +396,13 @@ class FaceAna:
         landmarks = self.trace.calculate(image, landmarks)
         hulls = [[np.min(l[:, 0]), np.min(l[:, 1]), np.max(l[:, 0]), np.max(l[:, 1])] for l in landmarks]
         self.track_box = self.judge_boxs(boxes_return, np.array(hulls))
+        ids = None
+        if self._ident is not None:      # output rows = the selected rows the landmark stage accepted, in order
+            valid = self.face_landmark.last_valid if len(boxes_return) else np.zeros((0,), bool)
+            src = [judge_src[self._sel_rows[q]] for q in range(len(boxes_return)) if valid[q]]
+            ids = self._ident.update([j for j, _ in src], [w for _, w in src], np.asarray(self.track_box, np.float64).reshape(-1, 4),
+                                     previous_track)
+        red = self._redact_with(ids[0] if ids else None)      # select [top_k] is [1, top_k] of the one frame
         chips = None
         if self.face_chips and len(landmarks):      # cut with the smoothed landmarks the result carries, from the resident frame
             c, m, v = self.engine.align_faces(None, np.asarray(landmarks)[None], chip_size=self.face_chips)
@@ -370,17 +416,17 @@ class FaceAna:
         redacted = red_jpeg = None
         if self.redact and len(landmarks):          # from the resident frame, with the smoothed landmarks the result carries
             if self._raw:
-                redacted = self.engine.redact_faces(None, np.asarray(landmarks)[None], **self.redact)[0]
+                redacted = self.engine.redact_faces(None, np.asarray(landmarks)[None], **red)[0]
             if self.jpeg:
-                red_jpeg = jpeg_redacted(self.engine, self.jpeg, self.redact, len(landmarks), (1,) + tuple(image.shape[:2]),
+                red_jpeg = jpeg_redacted(self.engine, self.jpeg, red, len(landmarks), (1,) + tuple(image.shape[:2]),
                                          source=(None, np.asarray(landmarks)[None]))
         self._keep_redacted(redacted, image, red_jpeg)
         over = None
         if self.draw and len(landmarks):            # on the resident frame, with the smoothed landmarks and the scores the result carries
-            over = draw_overlay(self.engine, self.draw, self.jpeg, self.redact, len(landmarks), (1,) + tuple(image.shape[:2]),
+            over = draw_overlay(self.engine, self.draw, self.jpeg, red, len(landmarks), (1,) + tuple(image.shape[:2]),
                                 np.asarray(states), source=(None, np.asarray(landmarks)[None]))
         self._keep_drawn(over, image)
-        return self.to_dict(self.track_box, landmarks, states, attrs, chips, self._keep_masks(masks, image), chip_jpeg, self._raw)
+        return self.with_ids(self.to_dict(self.track_box, landmarks, states, attrs, chips, self._keep_masks(masks, image), chip_jpeg, self._raw), ids)
 
     @property
     def _raw(self) -> bool:
@@ -468,6 +514,14 @@ class FaceAna:
             attach_masks(out, *masks)
         return out
 
+    @staticmethod
+    def with_ids(dicts, ids):
+        """Result dict i gets ``"id"`` and ``"age"`` from (ids, ages) of the same rows; ``None``: the dicts as they are."""
+        if ids is not None:
+            for d, i, a in zip(dicts, ids[0], ids[1]):
+                d["id"], d["age"] = int(i), int(a)
+        return dicts
+
     def diff_frames(self, previous_frame, image) -> bool:
         """True -> run the detector (facer.py:98-118): mean absolute difference of the frames > 5."""
         if previous_frame is None:
@@ -478,26 +532,35 @@ class FaceAna:
         return diff / previous_frame.shape[0] / previous_frame.shape[1] / 3.0 > self.diff_thres
 
     def sort_and_filter(self, bboxes):
+        """Leaves the input row of every returned row in ``_sel_rows`` (persistent ids)."""
+        self._sel_rows = []
         if len(bboxes) < 1:
             return []
         area = (bboxes[:, 2] - bboxes[:, 0]) * (bboxes[:, 3] - bboxes[:, 1])
         keep = area > self.min_face
+        rows = np.flatnonzero(keep)
         area, bboxes = area[keep], bboxes[keep, :]
         if bboxes.shape[0] > self.top_k:
             # equal areas: the later row first, as the reference's argsort gives under its pinned numpy (an insertion sort at
             # these sizes) and as track_select_kernel does; newer numpy sorts float32 with SIMD networks that keep no order
-            bboxes = bboxes[area.argsort(kind="stable")[-self.top_k:][::-1]]
+            order = area.argsort(kind="stable")[-self.top_k:][::-1]
+            bboxes, rows = bboxes[order], rows[order]
+        self._sel_rows = [int(r) for r in rows]
         return np.array(bboxes)
 
     def judge_boxs(self, previuous_bboxs, now_bboxs):
-        """Match each current box to the first previous box with IoU > thres and EMA-smooth it."""
+        """Match each current box to the first previous box with IoU > thres and EMA-smooth it.  Leaves (previous row or -1, that
+        IoU as a double) of every current row in ``_judge_src`` (persistent ids)."""
+        self._judge_src = [(-1, 0.0)] * len(now_bboxs)
         if previuous_bboxs is None:
             return now_bboxs
         out = []
         for i in range(now_bboxs.shape[0]):
             for j in range(previuous_bboxs.shape[0]):
-                if _box_iou(now_bboxs[i], previuous_bboxs[j]) > self.iou_thres:
+                iou = _box_iou(now_bboxs[i], previuous_bboxs[j])
+                if iou > self.iou_thres:
                     out.append(self.smooth(now_bboxs[i], previuous_bboxs[j]))
+                    self._judge_src[i] = (j, float(iou))
                     break
             else:
                 out.append(now_bboxs[i][0:4])
@@ -510,6 +573,8 @@ class FaceAna:
         self.track_box = None
         self.previous_image = None
         self.previous_box = None
+        if self._ident is not None:
+            self._ident.reset()
         if self.device_tracking:
             self.engine.track_reset()
         self.engine.forget_frames()

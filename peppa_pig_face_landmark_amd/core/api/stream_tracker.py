@@ -17,6 +17,7 @@ import numpy as np
 from ... import _native
 from ...logger.logger import logger
 from .facer import FaceAna, _load_weights, draw_options, draw_overlay, get_cfg, jpeg_chips, jpeg_options, jpeg_redacted, stage_options
+from ..smoother.ident import ids_options, spare_select
 from .hip_model_base import HIPEngine, run_guarded
 
 
@@ -24,8 +25,14 @@ class StreamTracker:
     def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, max_streams: int = 8,
                  device: Optional[int] = None, library: Optional[str] = None, verbose: bool = False,
                  face_attributes: Optional[bool] = None, face_chips: Optional[int] = None,
-                 face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None, draw=None):
-        """``draw`` (default: ``Engine.draw`` of Skps.yml, off): the dict of ``FaceAna``; ``last_drawn`` (stream id -> uint8 [H,W,3])
+                 face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None, draw=None,
+                 track_ids=None, spare_ids: Optional[Dict[int, set]] = None):
+        """``track_ids`` (default: ``Engine.track_ids`` of Skps.yml, off): the option of ``FaceAna``; every result dict gets
+        ``"id"`` and ``"age"``.  Ids are per stream: unique across streams is (stream id, id).  ``spare_ids`` (stream id -> set of
+        ids, needs ``track_ids``; may be changed between calls through the attribute): with ``redact`` on, a face of stream s whose
+        id is in ``spare_ids[s]`` is not redacted, every other face is.
+
+        ``draw`` (default: ``Engine.draw`` of Skps.yml, off): the dict of ``FaceAna``; ``last_drawn`` (stream id -> uint8 [H,W,3])
         keeps the frames of the last call with the faces the results carry drawn on, ``last_drawn_jpeg`` (stream id -> bytes) their
         files with ``jpeg`` on.
 
@@ -67,6 +74,10 @@ class StreamTracker:
         self.draw = draw_options(draw, eng_cfg, self.redact)
         self.last_drawn: Optional[Dict[int, np.ndarray]] = None
         self.last_drawn_jpeg: Optional[Dict[int, bytes]] = None
+        self.track_ids = ids_options(track_ids, eng_cfg)
+        if spare_ids is not None and not self.track_ids:
+            raise ValueError("spare_ids needs track_ids on")
+        self.spare_ids: Dict[int, set] = {int(s): set(v) for s, v in (spare_ids or {}).items()}
         self.last_label_maps: Dict[int, np.ndarray] = {}
         self.last_owner_maps: Dict[int, np.ndarray] = {}
         self.max_streams = int(max_streams)
@@ -85,6 +96,8 @@ class StreamTracker:
                                   max_batch=self.max_streams * self.top_k, engine=self.engine, arch=kps_arch,
                                   face_attrs=self.face_attributes)
         self.engine.track_streams_config(self.max_streams, self.top_k)
+        if self.track_ids:
+            self.engine.track_ids_config(True, self.track_ids["keep_lost"])
         self.last_detector_ran: Dict[int, bool] = {}
         logger.info("stream tracker init done (%d streams)", self.max_streams)
 
@@ -101,17 +114,23 @@ class StreamTracker:
 
         def call(*args):
             r = self.engine.track_streams(*args)
-            attrs = chips = masks = redacted = red_jpeg = chip_jpeg = None
+            attrs = chips = masks = redacted = red_jpeg = chip_jpeg = ident = None
             raw = not self.jpeg or self.jpeg["raw"]
+            red = self.redact
+            if self.track_ids:                         # ids / ages of the call's [n][top_k] rows, and the select they imply
+                ident = self.engine.track_ids(len(r) * K)
+                if self.redact:
+                    red = dict(self.redact, select=np.concatenate(
+                        [spare_select(ident[0][i * K:(i + 1) * K], self.spare_ids.get(s)) for i, s in enumerate(ids)]))
             if self.draw:                              # the scores of the call's [n][top_k] rows, compacted like kps
                 sc = np.zeros((len(r), K, 98), np.float32)
                 for i, (b, _, s_i, _) in enumerate(r):
                     sc[i, :len(b)] = s_i
-                over[:] = draw_overlay(self.engine, self.draw, self.jpeg, self.redact, len(r) * K, batch.shape, sc.reshape(-1, 98))
+                over[:] = draw_overlay(self.engine, self.draw, self.jpeg, red, len(r) * K, batch.shape, sc.reshape(-1, 98))
             if self.redact and raw:
-                redacted = self.engine.face_redact(len(r) * K, **self.redact)[0]      # one frame per listed stream
+                redacted = self.engine.face_redact(len(r) * K, **red)[0]      # one frame per listed stream
             if self.redact and self.jpeg:
-                red_jpeg = jpeg_redacted(self.engine, self.jpeg, self.redact, len(r) * K, batch.shape)
+                red_jpeg = jpeg_redacted(self.engine, self.jpeg, red, len(r) * K, batch.shape)
             if self.face_attributes:
                 a = self.engine.face_attrs(len(r) * K)           # [n][top_k] rows, compacted like kps
                 attrs = [a[i * K:i * K + len(b)] for i, (b, _, _, _) in enumerate(r)]
@@ -124,8 +143,8 @@ class StreamTracker:
             if self.face_masks:
                 lab, own, mb, mv = self.engine.face_masks(len(r) * K)        # one map per listed stream, slots = the same rows
                 masks = [(lab[i], own[i], mb[i * K:(i + 1) * K], mv[i * K:(i + 1) * K]) for i in range(len(r))]
-            return r, attrs, chips, masks, redacted, red_jpeg, chip_jpeg
-        res, attrs, chips, masks, redacted, red_jpeg, chip_jpeg = run_guarded([self.detector, self.landmark], call, ids, batch,
+            return r, attrs, chips, masks, redacted, red_jpeg, chip_jpeg, ident
+        res, attrs, chips, masks, redacted, red_jpeg, chip_jpeg, ident = run_guarded([self.detector, self.landmark], call, ids, batch,
                                  float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]), float(self.min_face),
                                  float(self.iou_thres), float(self.alpha), float(self.diff_thres), planted)
         self.last_detector_ran = {s: ran for s, (_, _, _, ran) in zip(ids, res)}   # did the gate run the detector
@@ -140,9 +159,11 @@ class StreamTracker:
         if masks is not None:
             self.last_label_maps = {s: m[0] for s, m in zip(ids, masks)}
             self.last_owner_maps = {s: m[1] for s, m in zip(ids, masks)}
-        return {s: self.to_dict(b, k, sc, attrs[i] if attrs is not None else None, chips[i] if chips is not None else None,
-                                masks[i] if masks is not None else None, chip_jpeg[i] if chip_jpeg is not None else None,
-                                not self.jpeg or self.jpeg["raw"])
+        return {s: FaceAna.with_ids(
+                    self.to_dict(b, k, sc, attrs[i] if attrs is not None else None, chips[i] if chips is not None else None,
+                                 masks[i] if masks is not None else None, chip_jpeg[i] if chip_jpeg is not None else None,
+                                 not self.jpeg or self.jpeg["raw"]),
+                    None if ident is None else (ident[0][i * K:(i + 1) * K], ident[1][i * K:(i + 1) * K]))
                 for i, (s, (b, k, sc, _)) in enumerate(zip(ids, res))}
 
     to_dict = staticmethod(FaceAna.to_dict)

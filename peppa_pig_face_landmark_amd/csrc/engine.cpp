@@ -109,6 +109,7 @@ struct pf_handle {
     // tracking state of the handle's video stream (pf_track_frame: one slot) and of its pf_track_streams pool (k_track.h)
     TrackPool track;
     TrackPool streams;
+    int track_ids = 0, track_keep_lost = 0;   // pf_track_ids_config: persistent ids of both pools on / off, frames a lost id is kept
     JpegState jpeg;          // pf_decode_jpeg (jpeg.inl)
     JpegEncState jpeg_enc;   // pf_encode_jpeg (jpeg_enc.inl): tables and scratch of its three kernels
     // f32s range guard (pf_common.h pf_amax, k_layers.h range_verdict_kernel): on for every forward unless switched off with

@@ -7,6 +7,7 @@
 //   note_frameless()  pf_landmark_forward: rows without a frame (the accessors say so); its attribute rows follow
 //   note_frames()     rows [F][per_frame] and the frame each group of per_frame rows is read from, ready-made
 //   note_attrs()      attribute rows of kind 1, 2 or 3 (below)
+//   note_ids()        persistent ids and ages of the rows (the tracking calls while pf_track_ids_config has them on; pf_track_ids)
 #pragma once
 #include <algorithm>
 #include <utility>
@@ -29,9 +30,12 @@ struct FaceRows {
     const float* attr_src = nullptr;
     std::vector<int> h_attr_valid;
     int* d_attr_valid = nullptr; size_t attr_valid_bytes = 0;
+    // persistent ids / ages of the rows (the tracker pool's out_id / out_age and the host copies the call brought back), or nullptr
+    const int* ids = nullptr; const int* ages = nullptr;
+    const int* h_ids = nullptr; const int* h_ages = nullptr;
 
-    void forget() { kind = 0; attr_kind = 0; }
-    void forget_frames() { kind = 0; }
+    void forget() { kind = 0; attr_kind = 0; ids = ages = h_ids = h_ages = nullptr; }
+    void forget_frames() { kind = 0; ids = ages = h_ids = h_ages = nullptr; }
     void note_frameless() { kind = 2; attr_kind = 0; }
     void note_frames(std::vector<AlignFrame> table, int n_rows, int rows_per_frame, const void* d_kps, int f64, const int* d_counts,
                      const int* d_valid = nullptr, int stride = 0) {
@@ -40,6 +44,9 @@ struct FaceRows {
         counts = d_counts; valid = d_valid; valid_stride = stride;
     }
     void note_attrs(int k, int n_rows, const float* src = nullptr) { attr_kind = k; attr_rows = n_rows; attr_src = src; }
+    void note_ids(const int* d_ids, const int* d_ages, const int* host_ids, const int* host_ages) {
+        ids = d_ids; ages = d_ages; h_ids = host_ids; h_ages = host_ages;
+    }
     void release() {
         if (d_attr_valid) (void)hipFree(d_attr_valid);
         *this = FaceRows();

@@ -23,6 +23,7 @@
 #include "pf_common.h"
 
 const int kTrackMaxNow = 1024;   // rows NMS can keep per frame (judge_boxs input)
+const int kTrackMaxLost = 64;    // entries of a stream's lost list (persistent ids); also the most faces per frame ids are kept for
 
 // One frame of a tracking call (pf_track_frame: one; pf_track_streams: one per listed stream), built on the host after the
 // gate and uploaded once per call.  Every track kernel below has the frame index i as a grid dimension and finds its
@@ -59,6 +60,23 @@ struct TrackPoolView {
     double* out_box;     // [S][K][4]
     double* out_lm;      // [S][K][98][2]
     const TrackFrameDesc* desc;   // [S], the first n used
+    // ---- persistent face ids (pf_track_ids_config; the rule: include/peppa_hip.h).  State of slot s, rows at stride K:
+    int* id;             // [S][K] id of row r of track_box (0 = no id)
+    int* age;            // [S][K] frames that id has been seen
+    int* next_id;        // [S] ids handed out so far: the next fresh id is next_id + 1, never reused while the pool lives
+    int* lost_n;         // [S] entries of the lost list, in insertion order:
+    int* lost_id;        // [S][kTrackMaxLost]
+    int* lost_age;       // [S][kTrackMaxLost]
+    int* lost_gone;      // [S][kTrackMaxLost] frames the id has been absent
+    double* lost_box;    // [S][kTrackMaxLost][4] its last track box
+    // scratch of frame i: the provenance the stages record (written only while ids are on) and the ids in call order
+    int* match_j;        // [S][kTrackMaxNow] previous row a judged row was smoothed with, -1: none (track_judge_kernel)
+    double* match_w;     // [S][kTrackMaxNow] the IoU of that match
+    int* sel_src;        // [S][K] judged row (detector frame) or track row (gated frame) of every selected row (track_select_kernel)
+    double* prev_box;    // [S][K][4] track_box as it was before this frame, captured by track_select_kernel
+    int* prev_n;         // [S] rows of it (0 without a track)
+    int* out_id;         // [S][K] ids of frame i's rows at stride top_k, 0 beyond its count
+    int* out_age;        // [S][K]
     int K;               // faces per slot the pool was allocated for
     int top_k;           // faces per frame of this call (<= K)
     __device__ double* slot_lm(double* base, int slot, int half) const { return base + ((size_t)slot * 2 + half) * K * 196; }
@@ -88,9 +106,12 @@ struct TrackPool {
     std::vector<unsigned long long> h_sums;
     std::vector<double> h_box, h_lm;       // pf_track_frame: host staging of the results (trimmed to the count after the sync)
     std::vector<float> h_scores;
+    std::vector<int> h_ids;                // host copies of out_id / out_age of the last call (pf_track_ids)
     void release() {
         void* ptrs[] = {v.track_box, v.n_track, v.lm, v.dx, v.n_lm, v.f32, v.judged, v.n_judged, v.sel, v.n_sel, v.sel_f32,
-                        v.hull, v.scores, v.out_count, v.out_box, v.out_lm, d_desc, d_frames, d_sums, d_det_idx};
+                        v.hull, v.scores, v.out_count, v.out_box, v.out_lm, d_desc, d_frames, d_sums, d_det_idx,
+                        v.id, v.age, v.next_id, v.lost_n, v.lost_id, v.lost_age, v.lost_gone, v.lost_box, v.match_j, v.match_w,
+                        v.sel_src, v.prev_box, v.prev_n, v.out_id, v.out_age};
         for (void* p : ptrs) if (p) (void)hipFree(p);
         *this = TrackPool();
     }
@@ -151,6 +172,7 @@ struct JudgeStageArgs {
     int stage;
     const float* det_rows; const int* det_count; int det_stride;   // NMS output: [D][det_stride][16] rows, [D] counts
     double iou_thres, alpha;
+    int* match_j; double* match_w;     // persistent ids on, detections stage: TrackPoolView::match_j / match_w; nullptr otherwise
 };
 
 __global__ __launch_bounds__(256) void track_judge_kernel(JudgeStageArgs g) {
@@ -185,17 +207,22 @@ __global__ __launch_bounds__(256) void track_judge_kernel(JudgeStageArgs g) {
         double b[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) b[c] = a.now_f64 ? a.now_f64[(size_t)i * 4 + c] : (double)a.now_f32[(size_t)i * a.now_stride + c];
+        int mj = -1;
+        double mw = 0.0;
         for (int j = 0; j < np; ++j) {
             const double* p = a.prev + (size_t)j * 4;
-            if (pf_box_iou(b, n32, p, p32) > a.iou_thres) {
+            const double iou = pf_box_iou(b, n32, p, p32);
+            if (iou > a.iou_thres) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) b[c] = pf_ema(a.alpha, b[c], n32, p[c], p32);
                 if (!p32) s_mixed = 1;
+                mj = j; mw = iou;
                 break;
             }
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) a.out[(size_t)i * 4 + c] = b[c];
+        if (g.match_j) { g.match_j[(size_t)f * kTrackMaxNow + i] = mj; g.match_w[(size_t)f * kTrackMaxNow + i] = mw; }
     }
     __syncthreads();
     if (threadIdx.x == 0) { *a.n_out = n; *a.out_f32 = (n32 && !s_mixed) ? 1 : 0; }
@@ -207,6 +234,7 @@ __global__ __launch_bounds__(256) void track_judge_kernel(JudgeStageArgs g) {
 struct SelectArgs {
     TrackPoolView v;
     double min_face;
+    int ids;             // persistent ids on: record TrackPoolView::sel_src and capture prev_box / prev_n
 };
 
 __device__ __forceinline__ double pf_box_area(const double* b, int f32) {
@@ -214,9 +242,16 @@ __device__ __forceinline__ double pf_box_area(const double* b, int f32) {
 }
 
 __global__ __launch_bounds__(64) void track_select_kernel(SelectArgs g) {
-    if (threadIdx.x != 0) return;
     const int i = blockIdx.x;
     const TrackFrameDesc d = g.v.desc[i];
+    if (g.ids) {         // the previous track boxes, before the hull judge of this frame overwrites them (track_ident_kernel)
+        const int np = d.has_track ? min(g.v.n_track[d.slot], g.v.K) : 0;
+        const double* tb = g.v.track_box + (size_t)d.slot * kTrackMaxNow * 4;
+        for (int k = threadIdx.x; k < np * 4; k += 64) g.v.prev_box[(size_t)i * g.v.K * 4 + k] = tb[k];
+        if (threadIdx.x == 0) g.v.prev_n[i] = np;
+    }
+    if (threadIdx.x != 0) return;
+    int* src = g.ids ? g.v.sel_src + (size_t)i * g.v.top_k : nullptr;
     struct { const double* boxes; double* out; double min_face; int top_k; } a;
     const bool det = d.det >= 0;
     a.boxes = det ? g.v.judged + (size_t)i * kTrackMaxNow * 4 : g.v.track_box + (size_t)d.slot * kTrackMaxNow * 4;
@@ -232,6 +267,7 @@ __global__ __launch_bounds__(64) void track_select_kernel(SelectArgs g) {
             const double* b = a.boxes + (size_t)k * 4;
             if (pf_box_area(b, f32) > a.min_face) {
                 for (int c = 0; c < 4; ++c) a.out[nsel * 4 + c] = b[c];
+                if (src) src[nsel] = k;
                 nsel++;
             }
         }
@@ -250,6 +286,7 @@ __global__ __launch_bounds__(64) void track_select_kernel(SelectArgs g) {
             }
             if (bk < 0) break;
             for (int c = 0; c < 4; ++c) a.out[nsel * 4 + c] = a.boxes[(size_t)bk * 4 + c];
+            if (src) src[nsel] = bk;
             nsel++;
             last_area = best;
             last_k = bk;
@@ -390,6 +427,150 @@ __global__ void track_count_kernel(TrackPoolView v, const int* crop_params) {
     for (int k = 0; k < n; ++k) nv += crop_params[((size_t)i * v.top_k + k) * 8] != 0 ? 1 : 0;
     v.n_lm[(size_t)d.slot * 2 + nxt] = nv;
     v.f32[(size_t)d.slot * 4 + 2 + nxt] = 1;
+}
+
+// pf_box_iou_f64 with contraction switched off in the source: the lost-list comparison of the identity rule is restated in numpy
+// (core/smoother/ident.py), which never fuses a multiply into an add
+__device__ __forceinline__ double pf_box_iou_f64_strict(const double* a, const double* b) {
+#pragma clang fp contract(off)
+    const double s1 = (a[2] - a[0]) * (a[3] - a[1]);
+    const double s2 = (b[2] - b[0]) * (b[3] - b[1]);
+    const double x1 = fmax(a[0], b[0]), y1 = fmax(a[1], b[1]);
+    const double x2 = fmin(a[2], b[2]), y2 = fmin(a[3], b[3]);
+    const double inter = fmax(0.0, x2 - x1) * fmax(0.0, y2 - y1);
+    const double sum = s1 + s2;
+    return inter / (sum - inter);
+}
+
+// Persistent face ids: steps 1-6 of the identity rule (include/peppa_hip.h, "Persistent face ids") for frame i = blockIdx.x of the
+// call, one workgroup per frame like its neighbours.  ORDERING: one launch, BEHIND the hull judge, because step 5 compares the NEW
+// track boxes with the lost list; the PREVIOUS boxes that step 6 appends for rows that lose their id were captured in front of that
+// launch by track_select_kernel (prev_box / prev_n), together with the provenance of the selected rows (sel_src) and, on a detector
+// frame, of the judged rows (match_j / match_w, track_judge_kernel).  Everything is staged into LDS by all lanes, the IoU matrix
+// output rows x lost entries is filled by all lanes, then lane 0 resolves the conflicts, the claims and the list serially (at most
+// kTrackMaxLost rows against at most kTrackMaxLost entries, all in LDS) and all lanes write the state and the call-order ids back.
+// No atomics, no global scratch beyond the pool's arrays.  A slot without a track (first frame, after a reset) starts with no rows
+// and an empty list, which is how the resets forget ids without touching the device; next_id is left alone by them.
+struct IdentArgs {
+    TrackPoolView v;
+    const int* crop_params;   // [n][top_k][8], [0] = the landmark stage accepted the selected row
+    double iou_thres;
+    int keep_lost;            // 0 .. 255
+};
+
+__global__ __launch_bounds__(256) void track_ident_kernel(IdentArgs g) {
+    const int L = kTrackMaxLost;
+    __shared__ double s_iou[L * L];            // [output row][lost entry]
+    __shared__ double s_nbox[L * 4];           // new track boxes
+    __shared__ double s_lbox[2 * L * 4];       // lost boxes; the second half takes this frame's appends before the list is cut to L
+    __shared__ double s_w[L];
+    __shared__ int s_src[L], s_keeper[L], s_pid[L], s_page[L], s_id[L], s_age[L], s_claimed[L];
+    __shared__ int s_lid[2 * L], s_lage[2 * L], s_lgone[2 * L];
+    __shared__ int s_nl;
+    const int i = blockIdx.x, tid = threadIdx.x, K = g.v.top_k, KP = g.v.K;
+    const TrackFrameDesc d = g.v.desc[i];
+    const int s = d.slot;
+    const bool det = d.det >= 0;
+    const int n_prev = d.has_track ? min(g.v.prev_n[i], L) : 0;
+    const int n_lost = (d.has_track && g.keep_lost > 0) ? min(g.v.lost_n[s], L) : 0;
+    const int n_sel = min(g.v.n_sel[i], min(K, L));
+    const int n_out = min(min(g.v.n_track[s], K), L);          // rows of the new track_box == output rows
+    const double* tb = g.v.track_box + (size_t)s * kTrackMaxNow * 4;
+    // ---- stage: previous ids, the lost list, the new boxes, source and weight of every output row (steps 1, 2)
+    if (tid < L) {
+        s_pid[tid] = tid < n_prev ? g.v.id[(size_t)s * KP + tid] : 0;
+        s_page[tid] = tid < n_prev ? g.v.age[(size_t)s * KP + tid] : 0;
+        s_claimed[tid] = 0;
+        s_src[tid] = -1;
+        s_w[tid] = 0.0;
+        if (tid < n_lost) {
+            s_lid[tid] = g.v.lost_id[(size_t)s * L + tid];
+            s_lage[tid] = g.v.lost_age[(size_t)s * L + tid];
+            s_lgone[tid] = g.v.lost_gone[(size_t)s * L + tid];
+        }
+    }
+    for (int k = tid; k < n_lost * 4; k += 256) s_lbox[k] = g.v.lost_box[(size_t)s * L * 4 + k];
+    for (int k = tid; k < n_out * 4; k += 256) s_nbox[k] = tb[k];
+    __syncthreads();
+    if (tid < n_sel && g.crop_params[((size_t)i * K + tid) * 8] != 0) {
+        int o = 0;                                              // output row = accepted selected rows before this one
+        for (int k = 0; k < tid; ++k) o += g.crop_params[((size_t)i * K + k) * 8] != 0 ? 1 : 0;
+        const int r = g.v.sel_src[(size_t)i * K + tid];
+        int j = det ? g.v.match_j[(size_t)i * kTrackMaxNow + r] : r;
+        const double w = det ? g.v.match_w[(size_t)i * kTrackMaxNow + r] : 0.0;
+        if (j >= n_prev || (j >= 0 && s_pid[j] == 0)) j = -1;   // a row without an id passes on no source
+        if (o < L) { s_src[o] = j; s_w[o] = j >= 0 ? w : 0.0; }
+    }
+    // ---- IoU of every output row with every lost entry
+    for (int k = tid; k < n_out * n_lost; k += 256) {
+        const int o = k / n_lost, e = k - o * n_lost;
+        s_iou[o * L + e] = pf_box_iou_f64_strict(s_nbox + o * 4, s_lbox + e * 4);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        // step 3: the greatest weight keeps a contested source, the lowest output row on equal weights
+        for (int j = 0; j < n_prev; ++j) s_keeper[j] = -1;
+        for (int o = 0; o < n_out; ++o) {
+            const int j = s_src[o];
+            if (j >= 0 && (s_keeper[j] < 0 || s_w[o] > s_w[s_keeper[j]])) s_keeper[j] = o;
+        }
+        // steps 4, 5
+        int next = g.v.next_id[s];
+        for (int o = 0; o < n_out; ++o) {
+            const int j = s_src[o];
+            if (j >= 0 && s_keeper[j] == o) { s_id[o] = s_pid[j]; s_age[o] = s_page[j] + 1; continue; }
+            int best = -1;
+            double bw = g.iou_thres;
+            for (int e = 0; e < n_lost; ++e)
+                if (!s_claimed[e] && s_iou[o * L + e] > bw) { best = e; bw = s_iou[o * L + e]; }
+            if (best >= 0) { s_id[o] = s_lid[best]; s_age[o] = s_lage[best] + 1; s_claimed[best] = 1; }
+            else { s_id[o] = ++next; s_age[o] = 1; }
+        }
+        g.v.next_id[s] = next;
+        // step 6
+        int m = 0;
+        for (int e = 0; e < n_lost; ++e) {
+            if (s_claimed[e] || s_lgone[e] + 1 > g.keep_lost) continue;
+            s_lid[m] = s_lid[e]; s_lage[m] = s_lage[e]; s_lgone[m] = s_lgone[e] + 1;
+            for (int c = 0; c < 4; ++c) s_lbox[m * 4 + c] = s_lbox[e * 4 + c];
+            ++m;
+        }
+        if (g.keep_lost > 0)
+            for (int j = 0; j < n_prev; ++j) {
+                if (s_pid[j] == 0 || s_keeper[j] >= 0) continue;
+                s_lid[m] = s_pid[j]; s_lage[m] = s_page[j]; s_lgone[m] = 1;
+                for (int c = 0; c < 4; ++c) s_lbox[m * 4 + c] = g.v.prev_box[((size_t)i * KP + j) * 4 + c];
+                ++m;
+            }
+        while (m > L) {                                         // the longest gone goes, the earliest inserted among equals
+            int worst = 0;
+            for (int e = 1; e < m; ++e) if (s_lgone[e] > s_lgone[worst]) worst = e;
+            for (int e = worst; e + 1 < m; ++e) {
+                s_lid[e] = s_lid[e + 1]; s_lage[e] = s_lage[e + 1]; s_lgone[e] = s_lgone[e + 1];
+                for (int c = 0; c < 4; ++c) s_lbox[e * 4 + c] = s_lbox[(e + 1) * 4 + c];
+            }
+            --m;
+        }
+        s_nl = m;
+    }
+    __syncthreads();
+    // ---- the slot's state and the ids of frame i in call order
+    const int m = s_nl;
+    if (tid == 0) g.v.lost_n[s] = m;
+    if (tid < m) {
+        g.v.lost_id[(size_t)s * L + tid] = s_lid[tid];
+        g.v.lost_age[(size_t)s * L + tid] = s_lage[tid];
+        g.v.lost_gone[(size_t)s * L + tid] = s_lgone[tid];
+    }
+    for (int k = tid; k < m * 4; k += 256) g.v.lost_box[(size_t)s * L * 4 + k] = s_lbox[k];
+    for (int k = tid; k < KP; k += 256) {
+        g.v.id[(size_t)s * KP + k] = k < n_out ? s_id[k] : 0;
+        g.v.age[(size_t)s * KP + k] = k < n_out ? s_age[k] : 0;
+    }
+    for (int k = tid; k < K; k += 256) {
+        g.v.out_id[(size_t)i * K + k] = k < n_out ? s_id[k] : 0;
+        g.v.out_age[(size_t)i * K + k] = k < n_out ? s_age[k] : 0;
+    }
 }
 
 // results of frame i, gathered from its slot into call order: the count (<= top_k), the new track boxes and the new

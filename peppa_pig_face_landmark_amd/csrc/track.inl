@@ -3,6 +3,26 @@
 // (included at the end of engine.cpp; kernels in k_track.h).  Both run the same stream-batched kernels (track_enqueue).
 namespace {
 
+// Identity state of every slot of a pool back to "no ids, empty lost lists, counters at 0" (a new pool, pf_track_ids_config); the
+// tracking state is left alone: rows whose id is 0 pass on no source and get fresh ids (rule step 1).  Ordered on the handle's stream.
+int track_ids_forget(pf_handle* h, TrackPool& P) {
+    if (!P.v.id) return 0;
+    const size_t s = (size_t)P.S, k = (size_t)P.K;
+    PF_HIP(h, hipMemsetAsync(P.v.id, 0, s * k * sizeof(int), h->stream));
+    PF_HIP(h, hipMemsetAsync(P.v.age, 0, s * k * sizeof(int), h->stream));
+    PF_HIP(h, hipMemsetAsync(P.v.next_id, 0, s * sizeof(int), h->stream));
+    PF_HIP(h, hipMemsetAsync(P.v.lost_n, 0, s * sizeof(int), h->stream));
+    return 0;
+}
+
+// Persistent ids are kept for at most kTrackMaxLost faces per frame.  Ids on and a pool of more faces never meet: whichever is asked
+// for second is refused here, by the entry point that asks, before it changes anything.
+int track_ids_fit(pf_handle* h, const char* who, int ids_on, int top_k) {
+    if (ids_on && top_k > kTrackMaxLost)
+        PF_FAIL(h, "%s: persistent ids are kept for at most %d faces per frame, top_k is %d", who, kTrackMaxLost, top_k);
+    return 0;
+}
+
 // (Re)allocate a pool of S slots for up to K faces each; every slot forgets its stream.
 int track_pool_alloc(pf_handle* h, TrackPool& P, int S, int K) {
     PF_HIP(h, hipStreamSynchronize(h->stream));
@@ -26,6 +46,22 @@ int track_pool_alloc(pf_handle* h, TrackPool& P, int S, int K) {
     PF_HIP(h, hipMalloc((void**)&v.sel_f32, s * sizeof(int)));
     PF_HIP(h, hipMalloc((void**)&v.out_count, s * sizeof(int)));
     PF_HIP(h, hipMalloc((void**)&P.d_desc, s * sizeof(TrackFrameDesc)));
+    // persistent ids (small next to the landmark sets, so allocated whether or not pf_track_ids_config switches them on)
+    PF_HIP(h, hipMalloc((void**)&v.id, s * k * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.age, s * k * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.next_id, s * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.lost_n, s * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.lost_id, s * kTrackMaxLost * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.lost_age, s * kTrackMaxLost * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.lost_gone, s * kTrackMaxLost * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.lost_box, s * kTrackMaxLost * 4 * sizeof(double)));
+    PF_HIP(h, hipMalloc((void**)&v.match_j, s * kTrackMaxNow * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.match_w, s * kTrackMaxNow * sizeof(double)));
+    PF_HIP(h, hipMalloc((void**)&v.sel_src, s * k * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.prev_box, s * k * 4 * sizeof(double)));
+    PF_HIP(h, hipMalloc((void**)&v.prev_n, s * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.out_id, s * k * sizeof(int)));
+    PF_HIP(h, hipMalloc((void**)&v.out_age, s * k * sizeof(int)));
     PF_HIP(h, hipMemset(v.f32, 0, s * 4 * sizeof(int)));
     PF_HIP(h, hipMemset(v.n_track, 0, s * sizeof(int)));
     PF_HIP(h, hipMemset(v.n_lm, 0, s * 2 * sizeof(int)));
@@ -35,7 +71,7 @@ int track_pool_alloc(pf_handle* h, TrackPool& P, int S, int K) {
     P.K = K;
     P.slots.assign(S, TrackSlot());
     P.h_desc.assign(S, TrackFrameDesc{});
-    return 0;
+    return track_ids_forget(h, P);        // a new pool counts its ids from 1
 }
 
 // pf_track_frame's pool: one slot, reallocated (and the stream forgotten) only when a call asks for more faces
@@ -57,6 +93,7 @@ int track_enqueue(pf_handle* h, TrackPool& P, int n, int top_k, const unsigned c
     const int rows = det.bufs[det.hdr.out_buf0].elems_per_item / 16;
     if (planted && n_det > 0 && planted_rows != rows) PF_FAIL(h, "pf_track: %d planted rows, the detector produces %d", planted_rows, rows);
     if (ensure_pipeline(h, std::max(n_det, 1), n * top_k, top_k, rows)) return 1;
+    const bool ids = h->track_ids != 0;      // no pool has more than kTrackMaxLost faces per frame then (track_ids_fit)
     TrackPoolView v = P.v;
     v.top_k = top_k;
     PF_HIP(h, hipMemcpyAsync(P.d_desc, P.h_desc.data(), (size_t)n * sizeof(TrackFrameDesc), hipMemcpyHostToDevice, h->stream));
@@ -82,11 +119,12 @@ int track_enqueue(pf_handle* h, TrackPool& P, int n, int top_k, const unsigned c
         ja.v = v; ja.stage = TRACK_JUDGE_DETECTIONS;
         ja.det_rows = h->pipe.d_keep_rows; ja.det_count = h->pipe.d_keep_count; ja.det_stride = kMaxKeep;
         ja.iou_thres = track_iou_thres; ja.alpha = smooth_box;
+        if (ids) { ja.match_j = v.match_j; ja.match_w = v.match_w; }      // which previous row each detection was smoothed with
         PF_LAUNCH(track_judge_kernel, dim3(n), dim3(256), h->stream, ja);
     }
     // 2. sort_and_filter -> boxes_return (float64 rows, stay on the device)
     SelectArgs sa{};
-    sa.v = v; sa.min_face = min_face;
+    sa.v = v; sa.min_face = min_face; sa.ids = ids ? 1 : 0;
     PF_LAUNCH(track_select_kernel, dim3(n), dim3(64), h->stream, sa);
     // 3. landmark stage on the selected boxes: n x top_k slots, the per-frame counts read on the device
     if (run_landmark_stage(h, d_frames, H, W, W * 3, h->pipe.d_sel_boxes, v.n_sel, n * top_k, top_k, v.sel, nullptr, v.sel_f32)) return 1;
@@ -107,6 +145,13 @@ int track_enqueue(pf_handle* h, TrackPool& P, int n, int top_k, const unsigned c
     jb.v = v; jb.stage = TRACK_JUDGE_HULLS;
     jb.iou_thres = track_iou_thres; jb.alpha = smooth_box;
     PF_LAUNCH(track_judge_kernel, dim3(n), dim3(256), h->stream, jb);
+    // 5b. persistent ids of the new rows (off unless pf_track_ids_config asked): one launch, behind the hull judge
+    if (ids) {
+        IdentArgs ia{};
+        ia.v = v; ia.crop_params = h->pipe.d_crop_params; ia.iou_thres = track_iou_thres; ia.keep_lost = h->track_keep_lost;
+        ProfScope ps(h, "track_ident");
+        PF_LAUNCH(track_ident_kernel, dim3(n), dim3(256), h->stream, ia);
+    }
     // 6. results in call order
     PF_LAUNCH(track_gather_kernel, dim3(n), dim3(256), h->stream, v);
     for (int i = 0; i < n; ++i) {
@@ -183,6 +228,7 @@ static int track_frame_impl(pf_handle* h, const uint8_t* bgr, int mem, int heigh
     Program& det = h->prog[PF_NET_DETECTOR];
     Program& lm = h->prog[PF_NET_LANDMARK];
     if (!det.loaded || !lm.loaded) PF_FAIL(h, "pf_track_frame: detector and landmark programs must be loaded");
+    if (track_ids_fit(h, "pf_track_frame", h->track_ids, top_k)) return 1;
     if (!bgr || !n_out || top_k < 1 || top_k > lm.max_batch) PF_FAIL(h, "pf_track_frame: bad arguments (top_k %d, landmark max_batch %d)", top_k, lm.max_batch);
     PF_HIP(h, hipSetDevice(h->device));
     if (ensure_track(h, top_k)) return 1;
@@ -214,6 +260,11 @@ static int track_frame_impl(pf_handle* h, const uint8_t* bgr, int mem, int heigh
     PF_HIP(h, hipMemcpyAsync(hb.data(), P.v.out_box, hb.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     PF_HIP(h, hipMemcpyAsync(hk.data(), P.v.out_lm, hk.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     PF_HIP(h, hipMemcpyAsync(hs.data(), P.v.scores, hs.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (h->track_ids) {      // ids and ages of the rows ride in the same batch of copies ([0, top_k) ids, [top_k, 2 top_k) ages)
+        P.h_ids.resize((size_t)2 * top_k);
+        PF_HIP(h, hipMemcpyAsync(P.h_ids.data(), P.v.out_id, (size_t)top_k * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        PF_HIP(h, hipMemcpyAsync(P.h_ids.data() + top_k, P.v.out_age, (size_t)top_k * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    }
     PF_HIP(h, hipStreamSynchronize(h->stream));
     if (check_numerics(h)) {
         // The range guard poisoned this frame's outputs with NaN, and steps 4-5 above have already folded them into the
@@ -230,6 +281,7 @@ static int track_frame_impl(pf_handle* h, const uint8_t* bgr, int mem, int heigh
     if (lm.hdr.out_buf2 >= 0) h->last.note_attrs(3, n, h->d_track_attrs);   // rows [n], like kps
     // pf_face_chips: the n compacted faces, their smoothed float64 landmarks, the resident frame
     h->last.note_frames(face_frames(h->pipe.d_cur, 0, 1, height, width, width * 3), n, top_k, P.v.out_lm, 1, nullptr);
+    if (h->track_ids) h->last.note_ids(P.v.out_id, P.v.out_age, P.h_ids.data(), P.h_ids.data() + top_k);
     if (n > 0) {
         if (boxes) memcpy(boxes, hb.data(), (size_t)n * 4 * sizeof(double));
         if (kps) memcpy(kps, hk.data(), (size_t)n * 196 * sizeof(double));
@@ -243,6 +295,7 @@ static int track_frame_impl(pf_handle* h, const uint8_t* bgr, int mem, int heigh
 int pf_track_streams_config(pf_handle* h, int max_streams, int top_k) {
     if (!h) return 1;
     if (max_streams < 1 || top_k < 1) PF_FAIL(h, "pf_track_streams_config: bad arguments (max_streams %d, top_k %d)", max_streams, top_k);
+    if (track_ids_fit(h, "pf_track_streams_config", h->track_ids, top_k)) return 1;
     PF_HIP(h, hipSetDevice(h->device));
     TrackPool& P = h->streams;
     h->last.forget_frames();      // the pool's frame slots and landmarks, which the rows of a pf_track_streams call point at, are replaced
@@ -251,6 +304,40 @@ int pf_track_streams_config(pf_handle* h, int max_streams, int top_k) {
     PF_HIP(h, hipMalloc((void**)&P.d_det_idx, (size_t)max_streams * sizeof(int)));
     P.h_sums.assign(max_streams, 0);
     P.h_det_idx.assign(max_streams, 0);
+    return 0;
+}
+
+int pf_track_ids_config(pf_handle* h, int enable, int keep_lost) {
+    if (!h) return 1;
+    if (keep_lost < 0 || keep_lost > 255) PF_FAIL(h, "pf_track_ids_config: keep_lost %d outside [0, 255]", keep_lost);
+    const int on = enable ? 1 : 0;
+    if (track_ids_fit(h, "pf_track_ids_config", on, std::max(h->track.K, h->streams.K))) return 1;
+    if (on == h->track_ids && keep_lost == h->track_keep_lost) return 0;
+    PF_HIP(h, hipSetDevice(h->device));
+    if (track_ids_forget(h, h->track) || track_ids_forget(h, h->streams)) return 1;
+    h->track_ids = on;
+    h->track_keep_lost = keep_lost;
+    h->last.note_ids(nullptr, nullptr, nullptr, nullptr);      // ids of an earlier call belong to the state just forgotten
+    return 0;
+}
+
+int pf_track_ids(pf_handle* h, int rows, int* ids, int* ages, int out_mem) {
+    if (!h) return 1;
+    if (rows < 0 || (out_mem != PF_MEM_HOST && out_mem != PF_MEM_DEVICE)) PF_FAIL(h, "pf_track_ids: bad arguments");
+    if (!h->track_ids) PF_FAIL(h, "pf_track_ids: persistent ids are off (pf_track_ids_config switches them on)");
+    const FaceRows* s = nullptr;
+    if (last_face_rows(h, "pf_track_ids", "no tracker and so no ids", rows, &s)) return 1;
+    if (!s->ids) PF_FAIL(h, "pf_track_ids: the handle's last call was not a tracking call (pf_track_frame* and pf_track_streams leave ids)");
+    if (rows == 0) return 0;
+    const size_t bytes = (size_t)rows * sizeof(int);
+    if (out_mem == PF_MEM_HOST) {            // the copies the tracking call itself brought back: no device traffic, no synchronisation
+        if (ids) memcpy(ids, s->h_ids, bytes);
+        if (ages) memcpy(ages, s->h_ages, bytes);
+        return 0;
+    }
+    PF_HIP(h, hipSetDevice(h->device));
+    if (ids) PF_HIP(h, hipMemcpyAsync(ids, s->ids, bytes, hipMemcpyDeviceToDevice, h->stream));
+    if (ages) PF_HIP(h, hipMemcpyAsync(ages, s->ages, bytes, hipMemcpyDeviceToDevice, h->stream));
     return 0;
 }
 
@@ -345,6 +432,11 @@ int pf_track_streams(pf_handle* h, int n, const int* stream_ids, const uint8_t* 
     if (boxes) PF_HIP(h, hipMemcpyAsync(boxes, P.v.out_box, (size_t)n * K * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (kps) PF_HIP(h, hipMemcpyAsync(kps, P.v.out_lm, (size_t)n * K * 196 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (scores) PF_HIP(h, hipMemcpyAsync(scores, P.v.scores, (size_t)n * K * 98 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (h->track_ids) {      // the same batch of copies: [0, n K) ids, [n K, 2 n K) ages
+        P.h_ids.resize((size_t)2 * n * K);
+        PF_HIP(h, hipMemcpyAsync(P.h_ids.data(), P.v.out_id, (size_t)n * K * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        PF_HIP(h, hipMemcpyAsync(P.h_ids.data() + (size_t)n * K, P.v.out_age, (size_t)n * K * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    }
     PF_HIP(h, hipStreamSynchronize(h->stream));
     if (check_numerics(h)) {
         // as in track_frame_impl: the poisoned outputs are already in the state of every stream of this call; those streams
@@ -359,6 +451,7 @@ int pf_track_streams(pf_handle* h, int n, const int* stream_ids, const uint8_t* 
     std::vector<AlignFrame> slots(n);
     for (int i = 0; i < n; ++i) slots[i] = AlignFrame{P.d_frames + (size_t)stream_ids[i] * P.frame_slot_bytes, height, width, width * 3, 0};
     h->last.note_frames(std::move(slots), n * K, K, P.v.out_lm, 1, P.v.out_count);
+    if (h->track_ids) h->last.note_ids(P.v.out_id, P.v.out_age, P.h_ids.data(), P.h_ids.data() + (size_t)n * K);
     return 0;
 }
 

@@ -9,6 +9,10 @@ around whole calls, each of which ends in a stream synchronisation; warm-up firs
 Prints one JSON line.
 
     python tools/bench_track_streams.py [--streams 1 8 32 96] [--repeat-share 0.5] [--dtype f32s]
+
+--ids KEEP_LOST measures the cost of persistent ids instead of the single-stream baseline: on ONE engine per point, ids off
+and ids on (pf_track_ids_config, that keep_lost) alternate, two repetitions of --min-seconds each, then a few profiled calls
+give the device time of track_ident_kernel (pf_profile_fetch).  --out FILE also writes the JSON there.
 """
 from __future__ import annotations
 
@@ -36,6 +40,8 @@ def parse_args():
     ap.add_argument("--dtype", default="f32s", choices=["f32", "f32s", "f16"])
     ap.add_argument("--min-seconds", type=float, default=1.0)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--ids", type=int, default=None, metavar="KEEP_LOST", help="measure persistent ids off / on instead of the baseline")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     return ap.parse_args()
 
 
@@ -102,6 +108,39 @@ def main():
 
         for c in range(args.warmup):
             step(c)
+        if args.ids is not None:
+            def timed(c0):
+                c, t0 = c0, time.perf_counter()
+                while True:
+                    step(c)
+                    c += 1
+                    el = time.perf_counter() - t0
+                    if el >= args.min_seconds and c - c0 >= period:
+                        return c, {"calls": c - c0, "ms_per_call": 1e3 * el / (c - c0), "frames_per_s": S * (c - c0) / el}
+            c, runs = args.warmup, {"off": [], "on": []}
+            for _ in range(2):                       # off, on, off, on: drift of the machine lands on both alike
+                for mode in ("off", "on"):
+                    eng.track_ids_config(mode == "on", args.ids)
+                    for _w in range(period):         # every stream has met its schedule in this mode (ids: their first frames)
+                        step(c)
+                        c += 1
+                    c, r = timed(c)
+                    runs[mode].append(r)
+            eng.track_ids_config(True, args.ids)
+            eng.profile_enable(True)
+            for _p in range(period):
+                step(c)
+                c += 1
+            prof = eng.profile_fetch().get("track_ident", (0.0, 0))
+            eng.profile_enable(False)
+            n_ids = int((eng.track_ids(S * K)[0] > 0).sum())
+            points.append({"streams": S, "keep_lost": args.ids, "off": runs["off"], "on": runs["on"], "ids_in_last_call": n_ids,
+                           "track_ident_kernel": {"launches": prof[1], "device_ms_per_launch": prof[0] / max(prof[1], 1)}})
+            eng.close()
+            del eng, batches, prows
+            pin.close()
+            torch.cuda.empty_cache()
+            continue
         c0 = c = args.warmup
         det = faces = 0
         t0 = time.perf_counter()
@@ -162,10 +201,14 @@ def main():
         pin.close()
         torch.cuda.empty_cache()
     probe.close()
-    print(json.dumps({"tool": "bench_track_streams", "device": torch.cuda.get_device_name(0), "dtype": args.dtype,
-                      "frame_hw": [H, W], "faces_per_frame": FACES, "top_k": K, "repeat_share": n_rep / CYCLE,
-                      "timing": "host wall clock over synchronised calls", "planted_rows": "pinned host, copied per detector frame",
-                      "points": points}))
+    line = json.dumps({"tool": "bench_track_streams", "device": torch.cuda.get_device_name(0), "dtype": args.dtype,
+                       "frame_hw": [H, W], "faces_per_frame": FACES, "top_k": K, "repeat_share": n_rep / CYCLE,
+                       "timing": "host wall clock over synchronised calls", "planted_rows": "pinned host, copied per detector frame",
+                       "points": points})
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":

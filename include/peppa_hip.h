@@ -221,6 +221,34 @@ int pf_draw_faces(pf_handle* h, const uint8_t* frames, int mem, int n_frames, in
 int pf_face_draw(pf_handle* h, int rows, const float* scores, const pf_draw_style* style,
                  const uint8_t* base, uint8_t* out, int* valid, int out_mem);
 
+/* Per-face region statistics (kernel face_stats_kernel, csrc/k_stats.h): a face turned into numbers about its
+ * pixels.  Everything is an exact integer sum, so every value is reproducible whatever the order of addition.
+ * The frame-space labels, owners, boxes and valid of pf_mask_faces are computed from the same landmarks, counts and live flags over
+ * ALL valid slots.  For frame pixel (x, y) with bytes c0, c1, c2 (BGR: channel 0 = B):
+ *   luma        Y = (29 c0 + 150 c1 + 77 c2 + 128) >> 8, in 0..255; a grey pixel of value v has Y = v
+ *   Laplacian   Lap = 4 Y(x, y) - Y(x-1, y) - Y(x+1, y) - Y(x, y-1) - Y(x, y+1); neighbour coordinates are clamped to the FRAME (edge
+ *               replication) and neighbours are read from the frame whatever their label or owner
+ *   dark iff Y <= dark, bright iff Y >= bright, with 0 <= dark < bright <= 255
+ * For slot k and label L in 1..8, over the pixels with owner == k + 1 and label == L, PF_STATS_FIELDS = 9 unsigned 64-bit values:
+ *   0 n   1 sum c0   2 sum c1   3 sum c2   4 sum Y   5 sum Y^2   6 sum Lap^2   7 number of dark pixels   8 number of bright pixels
+ * stats [F][top_k][8][9] uint64 (row L - 1 is label L); valid (optional) [F][top_k] as for pf_mask_faces.  Rows of invalid slots are
+ * left untouched, as for the chips; a valid slot that owns no pixel gets 72 zeros.  Owners are bytes, so top_k <= 255 (after
+ * pf_landmarks* at most 255 boxes) is required and refused otherwise.  frames, mem (host, device, or PF_MEM_RESIDENT with one frame),
+ * kps, kps_f64, kps_mem, counts and top_k as for pf_redact_faces.  Device output (out_mem = PF_MEM_DEVICE, stats 8-byte aligned) is
+ * enqueued on the handle's stream without a read-back; host output is produced in the handle's scratch, copied and synchronised.
+ * LIMITS: frame space only, no statistics of the chip; the maps are computed again when masks or a redaction are asked in the same
+ * step; sum Lap^2 / n is per FRAME pixel and therefore falls as a face grows; the face polygon stops at the upper brow line (no
+ * forehead); hard edges. */
+#define PF_STATS_FIELDS 9
+int pf_measure_faces(pf_handle* h, const uint8_t* frames, int mem, int n_frames, int height, int width,
+                     const void* kps, int kps_f64, int kps_mem, const int* counts, int top_k, int dark, int bright,
+                     uint64_t* stats, int* valid, int out_mem);
+/* The faces and frames of the handle's last pipeline call, measured: rows, refusals and messages those of pf_face_redact (the
+ * per-stream frame slots after pf_track_streams and a row stride other than 3 W included).  stats is [rows][8][9], valid [rows].  It
+ * reads the frames again: device frames the CALLER owns must still be alive and unchanged.  rows == 0 succeeds and writes nothing.
+ * The record of the last call is left alone. */
+int pf_face_stats(pf_handle* h, int rows, int dark, int bright, uint64_t* stats, int* valid, int out_mem);
+
 /* Detector forward == session.run of yolov5n-0.5.onnx (face_detector.py:29-31):
  * input float32 NCHW [1][3][384][640] RGB/255 or uint8 NHWC letterboxed RGB;
  * output [rows][16] decoded rows (cx,cy,w,h,obj,10 landmark coords,cls), rows = 15120 at 384x640. */
@@ -544,6 +572,9 @@ int pf_batch_face_redact(pf_batch* b, int rows, const int* select, int mode, int
  * memory; base (optional, device) and out are [n_frames][H][W][3] and offset per lane. */
 int pf_batch_face_draw(pf_batch* b, int rows, const float* scores, const pf_draw_style* style,
                        const uint8_t* base, uint8_t* out, int* valid, int out_mem);
+/* pf_face_stats of the lanes, gathered the same way: stats [rows][8][9] and valid [rows] of the last pf_batch_run_frames, each lane
+ * measuring the rows of the frames it ran, front mode on or off.  Device-resident frames of that call must still be alive. */
+int pf_batch_face_stats(pf_batch* b, int rows, int dark, int bright, uint64_t* stats, int* valid, int out_mem);
 
 /* Engine options.  PF_OPT_HIP_GRAPH = 1: pf_run_frames* calls whose buffers all live on the device are captured
  * into a hipGraph per distinct (pointers, shapes, thresholds) and replayed (launch-latency bound small batches). */

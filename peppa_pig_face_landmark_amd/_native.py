@@ -78,6 +78,12 @@ def _declare(lib):
         lib.pf_batch_face_redact.argtypes = [vp, i, vp, i, i, i, i, u, vp, vp, i]
         for name in ("pf_redact_faces", "pf_face_redact", "pf_batch_face_redact"):
             getattr(lib, name).restype = i
+    if hasattr(lib, "pf_measure_faces"):   # likewise
+        lib.pf_measure_faces.argtypes = [vp, vp, i, i, i, i, vp, i, i, vp, i, i, i, vp, vp, i]
+        lib.pf_face_stats.argtypes = [vp, i, i, i, vp, vp, i]
+        lib.pf_batch_face_stats.argtypes = [vp, i, i, i, vp, vp, i]
+        for name in ("pf_measure_faces", "pf_face_stats", "pf_batch_face_stats"):
+            getattr(lib, name).restype = i
     if hasattr(lib, "pf_draw_faces"):      # likewise
         lib.pf_draw_faces.argtypes = [vp, vp, i, i, i, i, vp, i, i, vp, vp, i, vp, vp, vp, i]
         lib.pf_face_draw.argtypes = [vp, i, vp, vp, vp, vp, vp, i]
@@ -257,6 +263,18 @@ def _last_call_redact(check, fn, fn_shape, handle, what, rows, select, args):
     sel = None if select is None else np.ascontiguousarray(select, np.int32).reshape(rows)
     check(fn(handle, rows, _ptr(sel), *args, _ptr(out), _ptr(valid), PF_MEM_HOST), what)
     return out, valid.astype(bool)
+
+
+PF_STATS_LABELS, PF_STATS_FIELDS = 8, 9
+
+
+def _last_call_stats(check, fn, handle, what, rows, dark, bright):
+    """Host-output pf_face_stats / pf_batch_face_stats."""
+    rows = int(rows)
+    stats = np.zeros((rows, PF_STATS_LABELS, PF_STATS_FIELDS), np.uint64)
+    valid = np.zeros((rows,), np.int32)
+    check(fn(handle, rows, int(dark), int(bright), _ptr(stats), _ptr(valid), PF_MEM_HOST), what)
+    return stats, valid.astype(bool)
 
 
 PF_DRAW_POINTS, PF_DRAW_CONTOURS, PF_DRAW_BOX = 1, 2, 4
@@ -606,6 +624,34 @@ class Engine:
         sel = None if select is None else np.ascontiguousarray(select, np.int32).reshape(int(rows))
         self._check(self.lib.pf_face_redact(self.h, int(rows), _ptr(sel), *_redact_args(mode, labels, strength, pad, colour), _ptr(d_out),
                                             _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE), "pf_face_redact")
+
+    # ---- per-face region statistics (include/peppa_hip.h pf_measure_faces / pf_face_stats) ----------------------------------------
+    def measure_faces(self, frames, kps: np.ndarray, counts: Optional[np.ndarray] = None, dark: int = 16, bright: int = 240, out=None):
+        """Exact integer statistics of the frame pixels each face owns, per label of mask_faces.  frames, kps and counts as for
+        redact_faces; a pixel is dark iff its luma <= ``dark`` and bright iff >= ``bright``.  Returns (stats uint64 [F,top_k,8,9] --
+        row L - 1 is label L; n, sum c0, sum c1, sum c2, sum Y, sum Y^2, sum Lap^2, dark pixels, bright pixels -- and valid bool
+        [F,top_k]); rows of invalid slots are left as they were (zero, or what ``out`` held).  ``core.api.quality.face_quality``
+        turns the sums into scores."""
+        k, f64, F, K = _kps_arg(kps)
+        fptr, mem, F, H, W, _keep = self._frames_arg(frames, F)
+        c = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
+        if out is None:
+            out = np.zeros((F, K, PF_STATS_LABELS, PF_STATS_FIELDS), np.uint64)
+        valid = np.zeros((F, K), np.int32)
+        self._check(self.lib.pf_measure_faces(self.h, fptr, mem, F, H, W, _ptr(k), f64, PF_MEM_HOST, _ptr(c), K, int(dark), int(bright),
+                                              _ptr(out), _ptr(valid), PF_MEM_HOST), "pf_measure_faces")
+        return out, valid.astype(bool)
+
+    def face_stats(self, rows: int, dark: int = 16, bright: int = 240):
+        """The statistics of the faces of the handle's last pf_landmarks / pf_run_frames / pf_track_frame / pf_track_streams call, in
+        that call's row order (include/peppa_hip.h pf_face_stats): (stats uint64 [rows,8,9], valid bool [rows]).  Device frames the
+        caller handed to that call must still be alive."""
+        return _last_call_stats(self._check, self.lib.pf_face_stats, self.h, "pf_face_stats", rows, dark, bright)
+
+    def face_stats_device(self, rows: int, d_stats: int, d_valid: int = 0, dark: int = 16, bright: int = 240):
+        """Same into device memory (8-byte aligned), enqueued on the handle's stream."""
+        self._check(self.lib.pf_face_stats(self.h, int(rows), int(dark), int(bright), _ptr(d_stats), _ptr(d_valid) if d_valid else None,
+                                           PF_MEM_DEVICE), "pf_face_stats")
 
     # ---- face overlay (include/peppa_hip.h pf_draw_faces / pf_face_draw) ------------------------------------------------------------
     def draw_faces(self, frames, kps: np.ndarray, counts: Optional[np.ndarray] = None, scores: Optional[np.ndarray] = None, out=None,
@@ -1244,6 +1290,20 @@ class BatchEngine:
         sel = None if select is None else np.ascontiguousarray(select, np.int32).reshape(int(rows))
         self._check(self.lib.pf_batch_face_redact(self.b, int(rows), _ptr(sel), *_redact_args(mode, labels, strength, pad, colour),
                                                   _ptr(d_out), _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE), "pf_batch_face_redact")
+
+    def measure_faces(self, frames, kps, **kw):
+        """Stage-level statistics on lane 0's engine (``Engine.measure_faces``)."""
+        return self.lane(0).measure_faces(frames, kps, **kw)
+
+    def face_stats(self, rows: int, dark: int = 16, bright: int = 240):
+        """The statistics of the faces of the last run_frames* call (include/peppa_hip.h pf_batch_face_stats), as
+        ``Engine.face_stats`` returns them; each lane measures the frames it ran."""
+        return _last_call_stats(self._check, self.lib.pf_batch_face_stats, self.b, "pf_batch_face_stats", rows, dark, bright)
+
+    def face_stats_device(self, rows: int, d_stats: int, d_valid: int = 0, dark: int = 16, bright: int = 240):
+        """Same into device memory, enqueued on the lanes' streams."""
+        self._check(self.lib.pf_batch_face_stats(self.b, int(rows), int(dark), int(bright), _ptr(d_stats),
+                                                 _ptr(d_valid) if d_valid else None, PF_MEM_DEVICE), "pf_batch_face_stats")
 
     def draw_faces(self, frames, kps, **kw):
         """Stage-level overlay on lane 0's engine (``Engine.draw_faces``)."""

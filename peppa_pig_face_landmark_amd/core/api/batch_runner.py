@@ -23,14 +23,18 @@ from ..smoother.lk import EmaFilter
 from .facer import (_box_iou, _load_weights, attach_masks, draw_options, draw_overlay, get_cfg, jpeg_chips, jpeg_options, jpeg_redacted,
                     stage_options)
 from .hip_model_base import _RANGE_ERR
+from .quality import attach_stats, stats_options
 
 
 class FrameBatchRunner:
     def __init__(self, cfg: Optional[dict] = None, weights: Optional[dict] = None, lanes: int = 3, frames_per_lane: int = 32,
                  device: Optional[int] = None, library: Optional[str] = None, graph: bool = True, top_k: Optional[int] = None,
                  face_attributes: Optional[bool] = None, face_chips: Optional[int] = None,
-                 face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None, draw=None):
-        """``draw`` (default: ``Engine.draw`` of Skps.yml, off): the dict of ``FaceAna``; ``last_drawn`` (uint8 [F,H,W,3]) keeps the
+                 face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None, draw=None, face_stats=None):
+        """``face_stats`` (default: ``Engine.face_stats`` of the configuration if present, else off): the option of ``FaceAna``;
+        every result dict gets ``"stats"`` and ``"quality"``, each lane measuring the frames it ran.
+
+        ``draw`` (default: ``Engine.draw`` of Skps.yml, off): the dict of ``FaceAna``; ``last_drawn`` (uint8 [F,H,W,3]) keeps the
         frames of the last ``run`` with the faces the results carry drawn on, each lane drawing the frames it ran, and
         ``last_drawn_jpeg`` (one ``bytes`` per frame) their files with ``jpeg`` on.
 
@@ -59,6 +63,8 @@ class FrameBatchRunner:
         self.last_redacted_jpeg = None
         self.draw = draw_options(draw, eng_cfg, self.redact)
         self.last_drawn = self.last_drawn_jpeg = None
+        self.face_stats = stats_options(face_stats, eng_cfg)
+        self._measured = None
         self.device = int(eng_cfg.get("device", 0)) if device is None else int(device)
         self.dtype = eng_cfg.get("dtype", "f32s")
         root = pathlib.Path(__file__).resolve().parents[2]
@@ -127,6 +133,9 @@ class FrameBatchRunner:
         r = self.engine.run_frames(frames, self.score_thrs, self.iou_thrs, self.min_face, self.top_k, planted_rows)
         F, K = r[0].shape[0], self.top_k
         attrs = self.engine.face_attrs(F * K).reshape(F, K, 7) if self.face_attributes else None
+        if self.face_stats:
+            st, sv = self.engine.face_stats(F * K, **self.face_stats)
+            self._measured = (st.reshape(F, K, 8, 9), sv.reshape(F, K))
         chips = None
         if self.face_chips:
             c, m, v = self.engine.face_chips(F * K, self.face_chips)
@@ -174,7 +183,7 @@ class FrameBatchRunner:
             chunk = frames[s:s + self.max_frames]
             attrs = chips = masks = redacted = red_jpeg = chip_jpeg = None
             planted = self._planted_rows(chunk) if self._planted_rows is not None else None
-            if self.face_attributes or self.face_chips or self.face_masks or self.redact or self.draw:
+            if self.face_attributes or self.face_chips or self.face_masks or self.redact or self.draw or self.face_stats:
                 if chunk.ndim != 4 or chunk.shape[-1] != 3 or chunk.dtype != np.uint8:
                     raise ValueError("frames must be uint8 [F,H,W,3]")
                 counts, boxes, kps, scores, attrs, chips, masks, redacted, red_jpeg, chip_jpeg = self._guarded(self._run_with_extras, chunk, planted)
@@ -198,6 +207,8 @@ class FrameBatchRunner:
                             d["chip_jpeg"] = chip_jpeg[f][i]
                 if masks is not None:
                     attach_masks(res, masks[0][f], masks[1][f], masks[2][f], masks[3][f])
+                if self.face_stats:
+                    attach_stats(res, self._measured[0][f], self._measured[1][f])
                 out.append(res)
             if masks is not None:
                 all_labels.append(masks[0]); all_owners.append(masks[1])

@@ -23,6 +23,7 @@ from ..smoother.lk import EmaFilter, GroupTrack
 from .face_detector import FaceDetector
 from .face_landmark import FaceLandmark
 from .hip_model_base import run_guarded
+from .quality import attach_stats, best_shots_options, stats_options
 
 
 def get_cfg(path: Optional[str] = None):
@@ -231,8 +232,17 @@ class FaceAna:
     def __init__(self, verbose: bool = False, cfg: Optional[dict] = None, weights: Optional[dict] = None,
                  device: Optional[int] = None, library: Optional[str] = None, face_attributes: Optional[bool] = None,
                  face_chips: Optional[int] = None, face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None, draw=None,
-                 track_ids=None, spare_ids=None):
-        """``track_ids`` (default: ``Engine.track_ids`` of Skps.yml, off): ``True`` or ``{"keep_lost": n}`` gives every result dict
+                 track_ids=None, spare_ids=None, face_stats=None, best_shots=None):
+        """``face_stats`` (default: ``Engine.face_stats`` of the configuration if present, else off): ``True`` or
+        ``{"dark": d, "bright": b}`` gives every result dict ``"stats"`` (uint64 [8,9]: per face-region label 1..8 the exact sums n,
+        c0, c1, c2, Y, Y^2, Lap^2 and the dark / bright pixel counts over the frame pixels the face owns, measured on the GPU with
+        the landmarks the result carries; include/peppa_hip.h pf_measure_faces) and ``"quality"`` (``quality.face_quality`` of it:
+        pixels, brightness, contrast, sharpness, dark, bright, skin_bgr), in both tracking modes.  Frame space only; sharpness is per
+        frame pixel and falls as a face grows; the face polygon has no forehead.  ``best_shots`` (``True`` or a dict with ``"key"`` /
+        ``"min_pixels"``; needs ``track_ids`` and ``face_stats``) keeps the best-scoring result of every id in ``self.best_shots``
+        (``quality.BestShots``), with its chip when ``face_chips`` is on.
+
+        ``track_ids`` (default: ``Engine.track_ids`` of Skps.yml, off): ``True`` or ``{"keep_lost": n}`` gives every result dict
         ``"id"`` (int, from 1, stable while the face is tracked; a face absent for up to ``keep_lost`` frames comes back with its id)
         and ``"age"`` (int, frames the id has been seen), in both tracking modes (the rule: include/peppa_hip.h, "Persistent face
         ids").  Geometric identity only (IoU, no appearance): two people who swap places behind an occlusion swap ids.  ``reset()``
@@ -306,7 +316,9 @@ class FaceAna:
         if spare_ids is not None and not self.track_ids:
             raise ValueError("spare_ids needs track_ids on")
         self.spare_ids = set(spare_ids or ())
-        self._planted_rows = None    # test instrument: callable returning decoded detector rows that replace the detector's own
+        self.face_stats = stats_options(face_stats, eng_cfg)
+        self.best_shots = best_shots_options(best_shots, self.track_ids, self.face_stats)
+        self._planted_rows = None   # test instrument: callable returning decoded detector rows that replace the detector's own
         self._det_cfg = sk["Detect"]
         self.top_k = sk["Detect"]["topk"]
         self.engine = _native.Engine(dev, library)      # one GPU, one stream, shared by both stages
@@ -365,7 +377,8 @@ class FaceAna:
                         if self.draw and n else None)
                 return r + (self.engine.face_attrs(n) if self.face_attributes else None, chips,
                             self.engine.face_masks(n) if self.face_masks and n else None,
-                            self.engine.face_redact(n, **red)[0] if self.redact and n and self._raw else None, jp, over, ids)
+                            self.engine.face_redact(n, **red)[0] if self.redact and n and self._raw else None, jp, over, ids,
+                            self.engine.face_stats(n, **self.face_stats) if self.face_stats and n else None)
             out = run_guarded(
                 [self.face_detector.model, self.face_landmark.model], fn, image, float(self._det_cfg["score_thrs"]), float(self._det_cfg["iou_thrs"]),
                 float(self.min_face), int(self.top_k), float(self.iou_thres), float(self.alpha), float(self.diff_thres),
@@ -375,7 +388,8 @@ class FaceAna:
             self.track_box = boxes
             self._keep_redacted(out[7], image, out[8][0])
             self._keep_drawn(out[9], image)
-            return self.with_ids(self.to_dict(boxes, kps, scores, out[4], out[5], self._keep_masks(out[6], image), out[8][1], self._raw), out[10])
+            return self._with_stats(self.with_ids(self.to_dict(boxes, kps, scores, out[4], out[5], self._keep_masks(out[6], image), out[8][1],
+                                                               self._raw), out[10]), out[11])
         diff = self.engine.set_frame(image)
         self.previous_image = image
         if diff is None or self.track_box is None or diff > self.diff_thres:
@@ -426,7 +440,21 @@ class FaceAna:
             over = draw_overlay(self.engine, self.draw, self.jpeg, red, len(landmarks), (1,) + tuple(image.shape[:2]),
                                 np.asarray(states), source=(None, np.asarray(landmarks)[None]))
         self._keep_drawn(over, image)
-        return self.with_ids(self.to_dict(self.track_box, landmarks, states, attrs, chips, self._keep_masks(masks, image), chip_jpeg, self._raw), ids)
+        measured = None
+        if self.face_stats and len(landmarks):      # on the resident frame, with the smoothed landmarks the result carries
+            st, sv = self.engine.measure_faces(None, np.asarray(landmarks)[None], **self.face_stats)
+            measured = (st[0], sv[0])
+        return self._with_stats(self.with_ids(self.to_dict(self.track_box, landmarks, states, attrs, chips, self._keep_masks(masks, image),
+                                                           chip_jpeg, self._raw), ids), measured)
+
+    def _with_stats(self, dicts, measured):
+        """(stats [n,8,9], valid [n]) of Engine.face_stats / measure_faces -> ``"stats"`` and ``"quality"`` of the result dicts, and
+        the update of ``best_shots``; ``None``: the dicts as they are."""
+        if measured is not None:
+            attach_stats(dicts, measured[0], measured[1])
+            if self.best_shots is not None:
+                self.best_shots.update(dicts)
+        return dicts
 
     @property
     def _raw(self) -> bool:

@@ -17,6 +17,7 @@ import numpy as np
 from ... import _native
 from ...logger.logger import logger
 from .facer import FaceAna, _load_weights, draw_options, draw_overlay, get_cfg, jpeg_chips, jpeg_options, jpeg_redacted, stage_options
+from .quality import attach_stats, best_shots_options, stats_options
 from ..smoother.ident import ids_options, spare_select
 from .hip_model_base import HIPEngine, run_guarded
 
@@ -26,8 +27,12 @@ class StreamTracker:
                  device: Optional[int] = None, library: Optional[str] = None, verbose: bool = False,
                  face_attributes: Optional[bool] = None, face_chips: Optional[int] = None,
                  face_masks: Optional[bool] = None, redact: Optional[dict] = None, jpeg=None, draw=None,
-                 track_ids=None, spare_ids: Optional[Dict[int, set]] = None):
-        """``track_ids`` (default: ``Engine.track_ids`` of Skps.yml, off): the option of ``FaceAna``; every result dict gets
+                 track_ids=None, spare_ids: Optional[Dict[int, set]] = None, face_stats=None, best_shots=None):
+        """``face_stats`` (default: ``Engine.face_stats`` of the configuration if present, else off) and ``best_shots``: the options
+        of ``FaceAna``; every result dict gets ``"stats"`` and ``"quality"``, and ``best_shots`` (a ``BestShots``) keeps the best
+        result of every (stream id, id).
+
+        ``track_ids`` (default: ``Engine.track_ids`` of Skps.yml, off): the option of ``FaceAna``; every result dict gets
         ``"id"`` and ``"age"``.  Ids are per stream: unique across streams is (stream id, id).  ``spare_ids`` (stream id -> set of
         ids, needs ``track_ids``; may be changed between calls through the attribute): with ``redact`` on, a face of stream s whose
         id is in ``spare_ids[s]`` is not redacted, every other face is.
@@ -78,6 +83,8 @@ class StreamTracker:
         if spare_ids is not None and not self.track_ids:
             raise ValueError("spare_ids needs track_ids on")
         self.spare_ids: Dict[int, set] = {int(s): set(v) for s, v in (spare_ids or {}).items()}
+        self.face_stats = stats_options(face_stats, eng_cfg)
+        self.best_shots = best_shots_options(best_shots, self.track_ids, self.face_stats)
         self.last_label_maps: Dict[int, np.ndarray] = {}
         self.last_owner_maps: Dict[int, np.ndarray] = {}
         self.max_streams = int(max_streams)
@@ -111,9 +118,12 @@ class StreamTracker:
         K = self.top_k
 
         over = [None, None]
+        measured = [None]
 
         def call(*args):
             r = self.engine.track_streams(*args)
+            if self.face_stats:                        # the call's [n][top_k] rows, compacted like kps
+                measured[0] = self.engine.face_stats(len(r) * K, **self.face_stats)
             attrs = chips = masks = redacted = red_jpeg = chip_jpeg = ident = None
             raw = not self.jpeg or self.jpeg["raw"]
             red = self.redact
@@ -159,12 +169,18 @@ class StreamTracker:
         if masks is not None:
             self.last_label_maps = {s: m[0] for s, m in zip(ids, masks)}
             self.last_owner_maps = {s: m[1] for s, m in zip(ids, masks)}
-        return {s: FaceAna.with_ids(
+        out = {s: FaceAna.with_ids(
                     self.to_dict(b, k, sc, attrs[i] if attrs is not None else None, chips[i] if chips is not None else None,
                                  masks[i] if masks is not None else None, chip_jpeg[i] if chip_jpeg is not None else None,
                                  not self.jpeg or self.jpeg["raw"]),
                     None if ident is None else (ident[0][i * K:(i + 1) * K], ident[1][i * K:(i + 1) * K]))
-                for i, (s, (b, k, sc, _)) in enumerate(zip(ids, res))}
+               for i, (s, (b, k, sc, _)) in enumerate(zip(ids, res))}
+        if measured[0] is not None:
+            for i, s in enumerate(ids):
+                attach_stats(out[s], measured[0][0][i * K:(i + 1) * K], measured[0][1][i * K:(i + 1) * K])
+                if self.best_shots is not None:
+                    self.best_shots.update(out[s], stream=s)
+        return out
 
     to_dict = staticmethod(FaceAna.to_dict)
 

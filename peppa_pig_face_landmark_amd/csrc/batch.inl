@@ -396,6 +396,16 @@ int pf_batch_face_redact(pf_batch* b, int rows, const int* select, int mode, int
     });
 }
 
+/* pf_face_stats of the lanes, gathered the same way: lane i measures the rows of the frames it ran */
+int pf_batch_face_stats(pf_batch* b, int rows, int dark, int bright, uint64_t* stats, int* valid, int out_mem) {
+    if (!b) return 1;
+    char buf[200];
+    if (const char* why = stats_check(dark, bright, b->attr_top_k, stats, out_mem, buf, sizeof(buf))) PF_BFAIL(b, "pf_batch_face_stats: %s", why);
+    return batch_lanes(b, "pf_batch_face_stats", "face rows", rows, true, [&](pf_handle* h, int, int r0, int nr) {
+        return pf_face_stats(h, nr, dark, bright, stats + (size_t)r0 * PF_STATS_ROW, valid ? valid + r0 : nullptr, out_mem);
+    });
+}
+
 /* pf_face_draw of the lanes, gathered the same way: lane i draws the frames it ran, base and out offset alike */
 int pf_batch_face_draw(pf_batch* b, int rows, const float* scores, const pf_draw_style* style, const uint8_t* base, uint8_t* out, int* valid,
                        int out_mem) {

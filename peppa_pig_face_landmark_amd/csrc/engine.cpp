@@ -38,6 +38,7 @@
 #include "k_align.h"
 #include "k_mask.h"
 #include "k_redact.h"
+#include "k_stats.h"
 #include "k_draw.h"
 #include "face_rows.h"
 #include "pf_program.h"
@@ -125,15 +126,16 @@ struct pf_handle {
     unsigned char comm_id[128] = {0};
     int comm_rank = -1, comm_world = 0;
     // what the handle's last call left for the stages behind the landmarks (face_rows.h): the rows with their frames, landmarks and
-    // live flags (pf_face_chips, pf_face_masks*, pf_face_redact) and the attribute rows (pf_face_attrs); written by its own functions only
+    // live flags (pf_face_chips, pf_face_masks*, pf_face_redact, pf_face_stats) and the attribute rows (pf_face_attrs); written by its own functions only
     FaceRows last;
     float* d_track_attrs = nullptr; size_t track_attrs_bytes = 0;      // attribute records of the tracking calls (FaceRows::attr_src)
-    StageUpload upload;      // host frames / landmarks / counts of pf_align_faces, pf_mask_faces, pf_redact_faces (stage_faces, face_rows.inl)
+    StageUpload upload;      // host frames / landmarks / counts of pf_align_faces, pf_mask_faces, pf_redact_faces, pf_measure_faces (stage_faces, face_rows.inl)
     AlignState align;        // aligned face chips (align.inl): scratch of its two kernels
     MaskState mask;          // face-region label maps (mask.inl): scratch of its two kernels
     // face redaction (redact.inl): the label maps it reads and the staging of host outputs
     RedactState redact;
-    DrawState draw;          // face overlay (draw.inl): the primitives of its two kernels and the staging of host outputs
+    StatsState stats;        // per-face region statistics (stats.inl): the label maps and owners it reads and the staging of host outputs
+    DrawState draw;         // face overlay (draw.inl): the primitives of its two kernels and the staging of host outputs
     // profiling
     bool profiling = false;
     std::map<std::string, ProfEntry> prof;
@@ -457,6 +459,7 @@ int pf_create(int device_id, pf_handle** out) {
         if (const char* v = getenv("PEPPA_ALIGN_LDS")) h->align.lds_budget = atoi(v);     // 0: every align_warp tile takes the direct path (tools/bench_face_chips.py)
         if (const char* v = getenv("PEPPA_MASK_NOCULL")) h->mask.no_cull = atoi(v) ? 1 : 0;       // 1: mask_fill evaluates every slot in every tile, no parity folding (tools/bench_face_masks.py)
         if (const char* v = getenv("PEPPA_REDACT_STAGE_ALL")) h->redact.stage_all = atoi(v) ? 1 : 0;       // 1: redact_kernel stages every tile through LDS, none is copied (tools/bench_face_redact.py)
+        if (const char* v = getenv("PEPPA_STATS_STAGED")) h->stats.staged = atoi(v) ? 1 : 0;       // 1: face_stats_staged_kernel, LDS-staged pieces and register partials, in place of face_stats_kernel (tools/bench_face_stats.py)
         if (const char* v = getenv("PEPPA_DRAW_NOCULL")) h->draw.no_cull = atoi(v) ? 1 : 0;       // 1: draw_kernel stages every tile and lists every primitive of the image in it (tools/bench_face_draw.py)
         if (const char* v = getenv("PEPPA_DET_TILE")) { if (sscanf(v, "%d,%d", &g_det_tile_th, &g_det_tile_tw) != 2) g_det_tile_th = g_det_tile_tw = 0; }
     }
@@ -511,6 +514,7 @@ void pf_destroy(pf_handle* h) {
     h->align.release();
     h->mask.release();
     h->redact.release();
+    h->stats.release();
     h->draw.release();
     h->track.release();
     h->streams.release();
@@ -761,6 +765,7 @@ int pf_profile_fetch(pf_handle* h, char* names, size_t names_cap, float* ms, int
 #include "align.inl"
 #include "mask.inl"
 #include "redact.inl"
+#include "stats.inl"
 #include "draw.inl"
 #include "pipeline.inl"
 #include "comm.inl"

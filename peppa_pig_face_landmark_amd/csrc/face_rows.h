@@ -1,5 +1,5 @@
 // What a handle's last call left on the device for the stages behind the landmarks: ONE record (pf_handle::last), read by pf_face_chips,
-// pf_face_masks, pf_face_masks_shape, pf_face_redact (the rows with their frames; checked reader: last_face_rows, face_rows.inl) and by
+// pf_face_masks, pf_face_masks_shape, pf_face_redact, pf_face_stats (the rows with their frames; checked reader: last_face_rows, face_rows.inl) and by
 // pf_face_attrs (the attribute rows), and written through its own functions and nowhere else:
 //   forget()          everything the record points at is about to be replaced: the pipeline and tracking calls on entry,
 //                     pf_load_program of the landmark slot, every lane of a pf_batch_run_frames
